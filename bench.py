@@ -28,10 +28,16 @@ Precision: ``--precision fp32`` (default) is the reference's serving precision
 TYPE_FP32): fp32 activations, split-product MFMA convs, detection parity with
 the fp32 models gated in ``tests/test_fp32_mode_gpu.py``.  ``--precision bf16``
 is a secondary, labelled number.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.
+``--dump-outputs DIR`` also writes the last timed step's detections as ``DIR/*.npy``
+(the same arrays in every run with the same arguments); ``--full`` adds the secondary
+measurements that take runs of their own after the timed steps.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -118,6 +124,16 @@ def parse():
                     help="launch/rendezvous check only: every rank joins, the ranks are counted with an all-reduce, "
                          "rank 0 prints them (no GPU work; used by the CPU tests with TCA_DIST_BACKEND=gloo)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the detections of the last timed step as they reach rank 0's "
+                         "host (what a caller of the step receives) to DIR/<branch>_<box|score|cls|count>.npy in "
+                         "float32, rows past each frame's count zeroed; the inputs are seeded, so two builds run "
+                         "with the same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements that need runs of their own after the timed steps: "
+                         "the DP gather / scatter alone (config.dp_comm_us_per_step, N > 1) and the GPU half of the "
+                         "JPEG decode alone (config.jpeg.gpu_idct_color_us_per_frame, --camera-input jpeg); a plain "
+                         "run times the steps and nothing else")
     ap.add_argument("--target-2d", type=float, default=100.0, help="candidates/frame reaching 2D NMS (calibration)")
     ap.add_argument("--target-3d", type=float, default=2000.0, help="anchors/frame reaching 3D NMS (calibration)")
     return ap.parse_args()
@@ -164,6 +180,56 @@ class _Split:
 
     def __call__(self):
         return self.fn()
+
+
+@contextlib.contextmanager
+def _reproducible_calibration():
+    """The head calibration runs the PyTorch modules once, before the steps.  Through MIOpen the
+    convolution algorithm, and with it the rounding of the calibrated weights, follows the tuning
+    records MIOpen keeps per user between runs: two runs with the same arguments gave camera scores
+    3.5e-5 apart.  PyTorch's own convolutions without atomic accumulation give every run the same
+    weights, so the timed path gets the same inputs and ``--dump-outputs`` the same arrays."""
+    was = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        with torch.backends.cudnn.flags(enabled=False):  # the switch that also governs MIOpen
+            yield
+    finally:
+        torch.use_deterministic_algorithms(was[0], warn_only=was[1])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, per_rank, branches) -> dict:
+    """``--dump-outputs``: the last timed step's detections on rank 0's host (``per_rank[r]``: the flat
+    ``outputs()`` list of rank r, four tensors per branch) as ``<branch>_<box|score|cls|count>.npy``,
+    float32 (class ids and counts are small integers: exact), the ranks' frames concatenated in rank
+    order.  Rows past a frame's count are not results (the buffers keep earlier steps' rows there) and
+    are written as zeros.  Above ``DUMP_LIMIT_BYTES`` in all, a fixed seeded sample of the frames is
+    written and ``frames.npy`` names them."""
+    arrays = {}
+    for j, br in enumerate(branches):
+        box, score, cls, count = (np.concatenate([np.asarray(per_rank[r][4 * j + i].numpy(), dtype=np.float32)
+                                                  for r in range(len(per_rank))]) for i in range(4))
+        if count.ndim == 1 and score.ndim == 2 and score.shape[0] == count.shape[0]:
+            live = np.arange(score.shape[1])[None, :] < count[:, None]
+            box, score, cls = np.where(live[..., None], box, 0), np.where(live, score, 0), np.where(live, cls, 0)
+        arrays.update({f"{br}_box": box, f"{br}_score": score, f"{br}_cls": cls, f"{br}_count": count})
+    total = sum(a.nbytes for a in arrays.values())
+    frames = min(a.shape[0] for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES and all(a.shape[0] == frames for a in arrays.values()):
+        keep = max(1, int(frames * DUMP_LIMIT_BYTES // total) - 1)
+        pick = np.sort(np.random.default_rng(0).choice(frames, keep, replace=False))
+        arrays = {k: a[pick] for k, a in arrays.items()}
+        arrays["frames"] = pick.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": path, "arrays": sorted(arrays), "bytes": total}
 
 
 def _preflight(info, dev, rccl_ranks: int, comm_used: str) -> dict:
@@ -336,13 +402,14 @@ def main():
                 lid.data.copy_(pc_host[0])
                 lid.frame_n.copy_(n_host[0])
     if args.ingest == "local" or info.is_main:
-        if use_cam:
-            calib["detectron_logit_shift" if det2 else "yolo_logit_shift"] = cam.calibrate_detection_density(
-                min(args.target_2d, 300.0) if det2 else args.target_2d)
-        if use_lid:
-            key = "centerpoint_hm_shift" if cp else ("second_iou_shift" if sec else "pp_logit_shift")
-            # SECOND-IoU: the target is RoIs (of the 100 proposals) passing the final score threshold
-            calib[key] = lid.calibrate_detection_density(min(args.target_3d, 60.0) if sec else args.target_3d)
+        with _reproducible_calibration():
+            if use_cam:
+                calib["detectron_logit_shift" if det2 else "yolo_logit_shift"] = cam.calibrate_detection_density(
+                    min(args.target_2d, 300.0) if det2 else args.target_2d)
+            if use_lid:
+                key = "centerpoint_hm_shift" if cp else ("second_iou_shift" if sec else "pp_logit_shift")
+                # SECOND-IoU: the target is RoIs (of the 100 proposals) passing the final score threshold
+                calib[key] = lid.calibrate_detection_density(min(args.target_3d, 60.0) if sec else args.target_3d)
     if info.world > 1:
         # every GPU must run the same model: rank 0's calibrated weights win
         from triton_client_amd.models.common import broadcast_parameters
@@ -788,11 +855,18 @@ def main():
     barrier(info)
     elapsed = time.perf_counter() - t0
     elapsed = allreduce_max(info, elapsed)
-    # DP communication alone, after the timed run (every rank takes part): the
+    dumped = None
+    if args.dump_outputs and info.is_main:
+        if host_out is None:
+            raise SystemExit("--dump-outputs needs at least one step")
+        # the synchronize above completed the last step's D2H into host_out[(it - 1) % 2]
+        dumped = dump_outputs(args.dump_outputs, host_out[(it[0] - 1) % 2],
+                              (["cam"] if use_cam else []) + (["lidar"] if use_lid else []))
+    # --full: DP communication alone, after the timed run (every rank takes part): the
     # detection gather (captured in the step graph when gather_in_graph) and the
     # --ingest rccl frame scatter, µs per step, max over ranks
     comm_us = None
-    if info.world > 1:
+    if info.world > 1 and args.full:
         def _time_us(fn, reps=10):
             barrier(info)
             torch.cuda.synchronize()
@@ -813,20 +887,23 @@ def main():
     jpeg_info = None
     if jdec is not None:
         host_us = jdec.host_us_per_frame()
-        # GPU half alone (IDCT + colour kernels), timed after the run
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        reps = 10
-        e0.record()
-        for _ in range(reps):
-            jdec.pending = 0
-            jdec.reconstruct(cam.frames)
-        e1.record()
-        torch.cuda.synchronize()
+        gpu_us = None
+        if args.full:
+            # GPU half alone (IDCT + colour kernels), timed after the run
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            reps = 10
+            e0.record()
+            for _ in range(reps):
+                jdec.pending = 0
+                jdec.reconstruct(cam.frames)
+            e1.record()
+            torch.cuda.synchronize()
+            gpu_us = round(1e3 * e0.elapsed_time(e1) / reps / B, 2)
         jpeg_info = {"decode_threads": args.decode_threads, "quality": args.jpeg_quality,
                      "avg_jpeg_bytes": int(np.mean([len(j) for j in jpegs])),
                      "host_entropy_decode_wall_us_per_frame": round(host_us, 1),
-                     "gpu_idct_color_us_per_frame": round(1e3 * e0.elapsed_time(e1) / reps / B, 2),
+                     "gpu_idct_color_us_per_frame": gpu_us,
                      "fallback_frames": jdec.stats["fallback"]}
 
     cam_name = {"yolov5n": "YOLOv5n-640 (COCO, 80 cls)", "yolov4": "YOLOv4-512 (COCO, 80 cls)",
@@ -907,6 +984,8 @@ def main():
                 "avg_2d_dets_per_frame": det2,
                 "avg_3d_dets_per_frame": det3,
                 "setup_plus_warmup_s": round(t0 - t_setup, 1),
+                "full": args.full,
+                "dumped_outputs": dumped,
                 "head_bias_calibration": {k: round(v, 3) for k, v in calib.items()},
                 "nms_candidates_target_per_frame": {"2d": args.target_2d, "3d": args.target_3d},
             },

@@ -220,12 +220,12 @@ def test_reference_model_repository_families():
     from triton_client_amd.server.repository import ModelRepository
     root = tempfile.mkdtemp()
     try:
-        for d, f in (("YOLOv5nCROP", "examples/YOLOv5/config.pbtxt"), ("YOLOv4", "examples/YOLOv4/config.pbtxt"),
-                     ("test_model", "examples/RetinaNet_detectron/config.pbtxt"),
-                     ("pointpillar_kitti", "examples/pointpillar_kitti/config.pbtxt")):
-            src = os.path.join("/root/reference", f)
-            if not os.path.exists(src):
-                pytest.skip("reference configs not mounted")
+        # the reference's examples/<family>/config.pbtxt, stored under tests/golden/model_configs
+        golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "model_configs")
+        for d, f in (("YOLOv5nCROP", "YOLOv5/config.pbtxt"), ("YOLOv4", "YOLOv4/config.pbtxt"),
+                     ("test_model", "RetinaNet_detectron/config.pbtxt"),
+                     ("pointpillar_kitti", "pointpillar_kitti/config.pbtxt")):
+            src = os.path.join(golden, f)
             os.makedirs(os.path.join(root, d))
             shutil.copy(src, os.path.join(root, d, "config.pbtxt"))
         repo = ModelRepository.from_directory(root, device="cpu", load=False)

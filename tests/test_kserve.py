@@ -54,13 +54,12 @@ def test_wire_parser_zero_copy_views():
 
 
 def test_reference_config_pbtxt_parses():
-    for f in ("examples/YOLOv5/config.pbtxt", "examples/pointpillar_kitti/config.pbtxt",
-              "examples/RetinaNet_detectron/config.pbtxt", "examples/YOLOv4/config.pbtxt"):
-        import os
-        p = os.path.join("/root/reference", f)
-        if not os.path.exists(p):
-            pytest.skip("reference not mounted")
-        cfg = parse_config_pbtxt(open(p).read())
+    # the reference's examples/<family>/config.pbtxt, stored under tests/golden/model_configs
+    import os
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "model_configs")
+    for f in ("YOLOv5/config.pbtxt", "pointpillar_kitti/config.pbtxt",
+              "RetinaNet_detectron/config.pbtxt", "YOLOv4/config.pbtxt"):
+        cfg = parse_config_pbtxt(open(os.path.join(golden, f)).read())
         assert cfg.name and len(cfg.input) >= 1 and len(cfg.output) >= 1
 
 
