@@ -82,6 +82,9 @@ def _run(bus, pub_topic, out_topic, out_type, messages, window, timeout):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--camera", type=int, default=512, help="CompressedImage messages (0: skip)")
+    ap.add_argument("--camera-encoding", default=None, metavar="NAME",
+                    help="publish raw sensor_msgs/Image messages in this encoding (rgb8, bgr8, rgba8, bgra8, mono8, "
+                         "mono16, yuv422, yuv422_yuy2, bayer_rggb8, ...) instead of JPEG CompressedImage")
     ap.add_argument("--lidar", type=int, default=512, help="PointCloud2 messages (0: skip)")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
@@ -146,16 +149,10 @@ def main():
     bus = TopicBus()
     window = 2 * a.batch * a.workers
     if a.camera:
-        jpegs = []
-        for s in range(8):
-            buf = io.BytesIO()
-            Image.fromarray(camera_frame(H, W, s)).save(buf, format="JPEG", quality=90)
-            jpegs.append(buf.getvalue())
         # header.seq strictly increasing over warm-up + run: the re-publisher drops a seq that is
         # not newer than the last one it published
         warm = 2 * a.batch
-        msgs_in = [msgs.CompressedImage(header=msgs.Header(seq=i + 1, frame_id="cam"), format="jpeg",
-                                        data=jpegs[i % 8]) for i in range(warm + a.camera)]
+        msgs_in = _camera_messages(H, W, warm + a.camera, a.camera_encoding)
         st = _Stages()
         drv = RosInference(engine=eng2, params={"sub_topic": "/cam", "pub_topic": "/cam_out"}, bus=bus,
                            batch=a.batch, workers=a.workers, metrics=st, queue_size=window)
@@ -167,8 +164,8 @@ def main():
         if info is not None:
             eng2.close()
         out["camera"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
-                         "input": f"CompressedImage JPEG {W}x{H} q90", "output": "annotated Image + Detection2DArray",
-                         "stages": st.summary()}
+                         "input": _camera_input(H, W, a.camera_encoding),
+                         "output": "annotated Image + Detection2DArray", "stages": st.summary()}
     if a.lidar:
         spec = LidarSpec(sensor_height=3.23)
         clouds = [compat.create_cloud_xyzi(np.frombuffer(lidar_sweep(spec, s).tobytes(), np.float32).reshape(-1, 4))
@@ -201,12 +198,23 @@ def main():
         shutdown(info)
 
 
-def _camera_messages(H, W, n):
+def _camera_input(H, W, encoding):
+    return f"CompressedImage JPEG {W}x{H} q90" if encoding is None else f"Image {encoding} {W}x{H}"
+
+
+def _camera_messages(H, W, n, encoding=None):
+    """n camera messages over 8 synthetic frames: JPEG CompressedImage, or raw Image in ``encoding``."""
     from PIL import Image
 
     from triton_client_amd.ros import msgs
     from triton_client_amd.utils.synthetic import camera_frame
 
+    if encoding is not None:
+        from triton_client_amd.ops.golden import image_packed_row, rgb8_to_encoding
+
+        raws = [rgb8_to_encoding(camera_frame(H, W, s), encoding) for s in range(8)]
+        return [msgs.Image(header=msgs.Header(seq=i + 1, frame_id="cam"), height=H, width=W, encoding=encoding,
+                           is_bigendian=0, step=image_packed_row(W, encoding), data=raws[i % 8]) for i in range(n)]
     jpegs = []
     for s in range(8):
         buf = io.BytesIO()
@@ -272,7 +280,7 @@ def _remote(a, H, W):
             eng = RemoteDetector2D(ch, client, letterbox=False, conf_thres=0.3, mode=a.mode, wire=a.wire,
                                    device=a.device)
             warm = 2 * a.batch
-            ms = _camera_messages(H, W, warm + a.camera)
+            ms = _camera_messages(H, W, warm + a.camera, a.camera_encoding)
             st = _Stages()
             drv = RosInference(None, client, engine=eng, params={"sub_topic": "/cam", "pub_topic": "/cam_out"},
                                bus=bus, batch=a.batch, workers=a.workers, metrics=st, queue_size=window)
@@ -285,8 +293,8 @@ def _remote(a, H, W):
             eng.release_transport()
             out["camera"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
                              "device_path": live is not None and live.stats["frames"] > 0,
-                             "input": f"CompressedImage JPEG {W}x{H} q90", "output": "annotated Image + Detection2DArray",
-                             "stages": st.summary()}
+                             "input": _camera_input(H, W, a.camera_encoding),
+                             "output": "annotated Image + Detection2DArray", "stages": st.summary()}
             ch.close()
         if a.lidar:
             ch = channel("pointpillar_kitti")

@@ -18,6 +18,10 @@ def main(argv=None) -> int:
     p.add_argument("--gt-topic", default="/camera/color/Detection2DArray")
     p.add_argument("--cam", default="720x1280")
     p.add_argument("--raw", action="store_true", help="raw rgb8 Image instead of JPEG")
+    p.add_argument("--encoding", default=None, metavar="NAME",
+                   help="raw Image in this sensor_msgs encoding (bgr8, rgba8, bgra8, mono8, mono16, yuv422, "
+                        "yuv422_yuy2, bayer_rggb8 / bggr8 / gbrg8 / grbg8); implies --raw")
+    p.add_argument("--row-pad", type=int, default=0, metavar="N", help="with --encoding: N padding bytes per row")
     p.add_argument("--no-camera", action="store_true")
     p.add_argument("--lidar", action="store_true")
     p.add_argument("--rings", type=int, default=64)
@@ -49,7 +53,12 @@ def main(argv=None) -> int:
                         draw_rect(img, x, y, x + w, y + h, (255, 255, 255), 1)
                     gm = detections_to_msg(g, msgs.Header(seq=s, stamp=t, frame_id="camera"))
                     bag.write(a.gt_topic, gm, t)
-                if a.raw:
+                if a.encoding is not None:
+                    from ..ops.golden import image_packed_row, rgb8_to_encoding
+                    step = image_packed_row(W, a.encoding) + a.row_pad
+                    m = msgs.Image(header=hdr, height=H, width=W, encoding=a.encoding, is_bigendian=0, step=step,
+                                   data=rgb8_to_encoding(img, a.encoding, step=step))
+                elif a.raw:
                     m = compat.numpy_to_imgmsg(img, "rgb8", header=hdr)
                 else:
                     m = msgs.CompressedImage(header=hdr, format="rgb8; jpeg compressed bgr8",

@@ -237,8 +237,10 @@ class LiveCamera:
 
     @staticmethod
     def host_rgb(msg_or_data, hw: Optional[Tuple[int, int]] = None) -> np.ndarray:
-        """Host decode for what the device path does not take (progressive JPEG,
-        PNG, bgr8 / mono8 / padded rows): HxWx3 uint8 RGB."""
+        """Host decode for what the device path does not take (progressive JPEG, PNG, JPEGs
+        the entropy decoder rejects, and every raw ``Image`` that is not packed rgb8: bgr8 /
+        rgba8 / bgra8, mono8 / mono16, YUV 4:2:2, 8-bit Bayer, padded rows): HxWx3 uint8 RGB.
+        ValueError for an ``Image`` encoding ``ops.golden.image_to_rgb8`` does not know."""
         from ..ros import compat
         if isinstance(msg_or_data, (bytes, bytearray, memoryview)):
             try:

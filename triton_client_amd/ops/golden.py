@@ -82,6 +82,133 @@ def preprocess_image(img: np.ndarray, dst_hw, mode="stretch", scale=(1 / 255.0,)
     return out.transpose(2, 0, 1).copy() if layout == "NCHW" else out
 
 
+# ----------------------------------------------------------------------------- sensor_msgs/Image -> rgb8
+# the encodings image_to_rgb8 takes (the values: stable codes for a device launcher)
+IMAGE_ENCODINGS = {"rgb8": 0, "bgr8": 1, "rgba8": 2, "bgra8": 3, "mono8": 4, "mono16": 5, "yuv422": 6,
+                   "yuv422_yuy2": 7, "bayer_rggb8": 8, "bayer_bggr8": 9, "bayer_gbrg8": 10, "bayer_grbg8": 11}
+_ENC_BPP = {"rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4, "mono8": 1, "mono16": 2, "yuv422": 2, "yuv422_yuy2": 2,
+            "bayer_rggb8": 1, "bayer_bggr8": 1, "bayer_gbrg8": 1, "bayer_grbg8": 1}
+# (row, column) of the red sample inside the 2x2 colour-filter tile: the ROS name spells the
+# colours of pixels (0,0), (0,1), (1,0), (1,1)
+_BAYER_RED = {"bayer_rggb8": (0, 0), "bayer_grbg8": (0, 1), "bayer_gbrg8": (1, 0), "bayer_bggr8": (1, 1)}
+# BT.601 limited range, 20-bit fixed point (OpenCV's COLOR_YUV2RGB_UYVY constants)
+_YUV_SHIFT, _YUV_CY, _YUV_CVR, _YUV_CVG, _YUV_CUG, _YUV_CUB = 20, 1220542, 1673527, -852492, -409993, 2116026
+
+
+def image_packed_row(width: int, encoding: str) -> int:
+    """Bytes of one row without padding; ValueError for an encoding ``image_to_rgb8`` does not take."""
+    if encoding not in _ENC_BPP:
+        raise ValueError(f"unsupported image encoding {encoding!r}")
+    return int(width) * _ENC_BPP[encoding]
+
+
+def check_image_geometry(height: int, width: int, step: int, encoding: str) -> int:
+    """The geometry checks of ``image_to_rgb8``; -> packed row bytes."""
+    packed = image_packed_row(width, encoding)
+    if height < 1 or width < 1:
+        raise ValueError(f"{encoding!r} image of {width}x{height}")
+    if encoding.startswith("yuv422") and width % 2:
+        raise ValueError(f"{encoding!r} needs an even width, not {width}")
+    if encoding.startswith("bayer") and (height < 2 or width < 2):
+        raise ValueError(f"{encoding!r} needs at least 2x2 pixels, not {width}x{height}")
+    if step < packed:
+        raise ValueError(f"{encoding!r} step {step} below the {packed} B of a {width}-pixel row")
+    return packed
+
+
+def image_to_rgb8(data, height: int, width: int, step: int, encoding: str, is_bigendian: int = 0) -> np.ndarray:
+    """What ``cv_bridge.imgmsg_to_cv2(msg, 'rgb8')`` makes of a raw ``sensor_msgs/Image``
+    payload: uint8 [H, W, 3].  Integer arithmetic throughout, so it can serve as the bit-exact
+    specification of a device kernel.  Bytes of a row past its packed size are ignored."""
+    H, W, step = int(height), int(width), int(step)
+    packed = check_image_geometry(H, W, step, encoding)
+    buf = np.frombuffer(data, np.uint8)
+    if buf.size < (H - 1) * step + packed:
+        raise ValueError(f"{encoding!r} image {W}x{H} step {step}: {buf.size} B of data")
+    rows = np.lib.stride_tricks.as_strided(buf, (H, packed), (step, 1))
+    if encoding in ("rgb8", "bgr8", "rgba8", "bgra8"):
+        a = rows.reshape(H, W, _ENC_BPP[encoding])[..., :3]
+        return np.ascontiguousarray(a[..., ::-1] if encoding.startswith("bgr") else a)
+    if encoding == "mono8":
+        return np.repeat(rows.reshape(H, W, 1), 3, axis=2)
+    if encoding == "mono16":
+        b = rows.reshape(H, W, 2).astype(np.int32)
+        v = (b[..., 0] << 8 | b[..., 1]) if is_bigendian else (b[..., 1] << 8 | b[..., 0])
+        g = ((v + 128) // 257).astype(np.uint8)
+        return np.repeat(g[..., None], 3, axis=2)
+    if encoding in ("yuv422", "yuv422_yuy2"):
+        m = rows.reshape(H, W // 2, 4).astype(np.int32)
+        if encoding == "yuv422":  # U0 Y0 V0 Y1
+            u, y0, v, y1 = (m[..., k] for k in range(4))
+        else:                     # Y0 U0 Y1 V0
+            y0, u, y1, v = (m[..., k] for k in range(4))
+        y = np.stack([y0, y1], axis=2).reshape(H, W)
+        u = np.repeat(u, 2, axis=1) - 128
+        v = np.repeat(v, 2, axis=1) - 128
+        yy = np.maximum(y - 16, 0) * _YUV_CY + (1 << (_YUV_SHIFT - 1))
+        out = np.empty((H, W, 3), np.uint8)
+        out[..., 0] = np.clip((yy + _YUV_CVR * v) >> _YUV_SHIFT, 0, 255)
+        out[..., 1] = np.clip((yy + _YUV_CVG * v + _YUV_CUG * u) >> _YUV_SHIFT, 0, 255)
+        out[..., 2] = np.clip((yy + _YUV_CUB * u) >> _YUV_SHIFT, 0, 255)
+        return out
+    # Bayer, bilinear, colour-filter plane extended by reflect-101 (keeps the colour parity)
+    p = np.pad(rows.astype(np.int32), 1, mode="reflect")
+    c = p[1:-1, 1:-1]
+    n, s, w, e = p[:-2, 1:-1], p[2:, 1:-1], p[1:-1, :-2], p[1:-1, 2:]
+    cross = (n + s + w + e + 2) >> 2
+    diag = (p[:-2, :-2] + p[:-2, 2:] + p[2:, :-2] + p[2:, 2:] + 2) >> 2
+    horiz, vert = (w + e + 1) >> 1, (n + s + 1) >> 1
+    ry, rx = _BAYER_RED[encoding]
+    yy, xx = np.mgrid[0:H, 0:W]
+    red_row, red_col = ((yy ^ ry) & 1) == 0, ((xx ^ rx) & 1) == 0
+    at_r, at_b = red_row & red_col, ~red_row & ~red_col
+    r = np.where(at_r, c, np.where(at_b, diag, np.where(red_row, horiz, vert)))
+    b = np.where(at_b, c, np.where(at_r, diag, np.where(red_row, vert, horiz)))
+    g = np.where(at_r | at_b, cross, c)
+    return np.stack([r, g, b], axis=2).astype(np.uint8)
+
+
+def rgb8_to_encoding(rgb: np.ndarray, encoding: str, step=None, is_bigendian: int = 0) -> bytes:
+    """Synthetic sensor data: an rgb8 frame [H, W, 3] as the ``H * step`` payload bytes of
+    ``encoding`` (mosaicked, chroma averaged over the pixel pair, or bytes permuted; padding
+    bytes are 0xA5).  A data generator, not a specification: ``image_to_rgb8`` of the result
+    is the original only where the encoding keeps it."""
+    rgb = np.asarray(rgb, np.uint8)
+    H, W = rgb.shape[:2]
+    packed = image_packed_row(W, encoding)
+    step = packed if step is None else int(step)
+    check_image_geometry(H, W, step, encoding)
+    c = rgb.astype(np.int32)
+    R, G, B = c[..., 0], c[..., 1], c[..., 2]
+    if encoding in ("rgb8", "bgr8"):
+        body = rgb if encoding == "rgb8" else rgb[..., ::-1]
+    elif encoding in ("rgba8", "bgra8"):
+        body = np.full((H, W, 4), 255, np.uint8)
+        body[..., :3] = rgb if encoding == "rgba8" else rgb[..., ::-1]
+    elif encoding in ("mono8", "mono16"):
+        gray = (77 * R + 150 * G + 29 * B + 128) >> 8
+        if encoding == "mono8":
+            body = gray.astype(np.uint8)
+        else:
+            body = (gray * 257).astype(">u2" if is_bigendian else "<u2").view(np.uint8)
+    elif encoding in ("yuv422", "yuv422_yuy2"):
+        y = np.clip(((66 * R + 129 * G + 25 * B + 128) >> 8) + 16, 16, 235)
+        u = np.clip(((-38 * R - 74 * G + 112 * B + 128) >> 8) + 128, 16, 240)
+        v = np.clip(((112 * R - 94 * G - 18 * B + 128) >> 8) + 128, 16, 240)
+        u = (u[:, 0::2] + u[:, 1::2] + 1) >> 1
+        v = (v[:, 0::2] + v[:, 1::2] + 1) >> 1
+        order = (u, y[:, 0::2], v, y[:, 1::2]) if encoding == "yuv422" else (y[:, 0::2], u, y[:, 1::2], v)
+        body = np.stack(order, axis=2).astype(np.uint8)
+    else:
+        ry, rx = _BAYER_RED[encoding]
+        yy, xx = np.mgrid[0:H, 0:W]
+        ch = (((yy ^ ry) & 1) + ((xx ^ rx) & 1))  # 0 at red, 1 at green, 2 at blue sites
+        body = np.take_along_axis(rgb, ch[..., None], axis=2)
+    out = np.full((H, step), 0xA5, np.uint8)
+    out[:, :packed] = np.ascontiguousarray(body).reshape(H, packed)
+    return out.tobytes()
+
+
 # ----------------------------------------------------------------------------- 2D NMS
 def box_iou_np(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     ix1 = np.maximum(a[:, None, 0], b[None, :, 0])

@@ -146,17 +146,16 @@ def spin(bus=None, timeout: Optional[float] = None) -> None:
 
 # ---------------------------------------------------------------- cv_bridge equivalents
 def imgmsg_to_numpy(msg: msgs.Image, desired_encoding: str = "rgb8") -> np.ndarray:
-    ch = {"rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4, "mono8": 1}[msg.encoding]
-    a = np.frombuffer(msg.data, np.uint8).reshape(msg.height, msg.step // 1)[:, : msg.width * ch]
-    a = a.reshape(msg.height, msg.width, ch)
-    if ch == 1:
-        a = np.repeat(a, 3, axis=2)
-    a = a[..., :3]
-    if desired_encoding == "rgb8" and msg.encoding.startswith("bgr"):
-        a = a[..., ::-1]
-    elif desired_encoding == "bgr8" and msg.encoding.startswith("rgb"):
-        a = a[..., ::-1]
-    return np.ascontiguousarray(a)
+    """``cv_bridge.imgmsg_to_cv2(msg, desired_encoding)`` for ``rgb8`` / ``bgr8``: HxWx3 uint8
+    from any encoding of :func:`triton_client_amd.ops.golden.image_to_rgb8` (8-bit colour,
+    mono8 / mono16, YUV 4:2:2, 8-bit Bayer; padded rows).  ValueError naming the encoding
+    for anything else."""
+    from ..ops.golden import image_to_rgb8
+
+    if desired_encoding not in ("rgb8", "bgr8"):
+        raise ValueError(f"unsupported desired_encoding {desired_encoding!r}")
+    a = image_to_rgb8(msg.data, msg.height, msg.width, msg.step, msg.encoding, getattr(msg, "is_bigendian", 0))
+    return np.ascontiguousarray(a[..., ::-1]) if desired_encoding == "bgr8" else a
 
 
 def numpy_to_imgmsg(img: np.ndarray, encoding: str = "rgb8", header: Optional[msgs.Header] = None) -> msgs.Image:
