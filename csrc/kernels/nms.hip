@@ -605,6 +605,109 @@ TCA_API int tca_box_iou(const float* a, int n, const float* b, int m, float* out
   TCA_LAUNCH_CHECK();
 }
 
+// ---- ragged pairwise rotated IoU for 3D evaluation (K14r) ---------------------
+// Every frame of an evaluation run in one launch: frame f owns predictions
+// pred_off[f] .. pred_off[f+1] and ground truth gt_off[f] .. gt_off[f+1]
+// (boxes x, y, z, dx, dy, dz, yaw; z the centre), and its [np_f, ng_f]
+// row-major IoU block starts at pair_off[f] in both outputs.  BEV IoU is that
+// of iou_bev() above; 3D follows OpenPCDet boxes_iou3d_gpu (overlap_bev times the
+// common height over the union volume).  One wave per (frame, 64 predictions),
+// found through a host-built tile table, so frames without predictions or
+// without ground truth cost no workgroup.  The frame's GT goes through LDS 64
+// boxes at a time (sincos once per box); lane = prediction walks the chunk with
+// broadcast LDS reads, results pass through a padded LDS tile and leave as one
+// contiguous run per prediction row (the whole tile is one run when the frame's
+// GT fits a chunk).  With class arrays, a pair of different classes is 0 / 0
+// and never evaluated.
+namespace {
+constexpr int kIouTile = 64;             // predictions per workgroup, one per lane
+constexpr int kIouChunk = 64;            // GT boxes per LDS round
+constexpr int kIouLd = kIouChunk + 1;    // padded row: lane-major writes and row-major reads both conflict-free
+
+__global__ void __launch_bounds__(64) box3d_iou_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                       const int* __restrict__ pred_cls,
+                                                       const int* __restrict__ gt_cls,
+                                                       const int* __restrict__ pred_off,
+                                                       const int* __restrict__ gt_off,
+                                                       const int* __restrict__ pair_off,
+                                                       const int* __restrict__ tile_frame,
+                                                       const int* __restrict__ tile_first,
+                                                       float* __restrict__ out_bev, float* __restrict__ out_3d) {
+  __shared__ float s_g[kIouChunk][12];  // x y z dx dy dz yaw cos sin
+  __shared__ int s_gc[kIouChunk];
+  __shared__ float s_bev[kIouTile * kIouLd], s_3d[kIouTile * kIouLd];
+  const int lane = threadIdx.x;
+  const int f = tile_frame[blockIdx.x], p0 = tile_first[blockIdx.x];
+  const int pb = pred_off[f], gb = gt_off[f], ng = gt_off[f + 1] - gb;
+  const int rows = min(kIouTile, pred_off[f + 1] - pb - p0);
+  const long obase = (long)pair_off[f] + (long)p0 * ng;
+  const bool by_cls = pred_cls != nullptr;
+  float A[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ca = 1.f, sa = 0.f;
+  int pc = 0;
+  if (lane < rows) {
+    const float* a = pred + (long)(pb + p0 + lane) * 7;
+#pragma unroll
+    for (int d = 0; d < 7; ++d) A[d] = a[d];
+    sincosf(A[6], &sa, &ca);
+    if (by_cls) pc = pred_cls[pb + p0 + lane];
+  }
+  const float va = A[3] * A[4] * A[5], alo = A[2] - 0.5f * A[5], ahi = A[2] + 0.5f * A[5];
+  for (int g0 = 0; g0 < ng; g0 += kIouChunk) {
+    const int cn = min(kIouChunk, ng - g0);
+    if (lane < cn) {
+      const float* c = gt + (long)(gb + g0 + lane) * 7;
+#pragma unroll
+      for (int d = 0; d < 7; ++d) s_g[lane][d] = c[d];
+      sincosf(c[6], &s_g[lane][8], &s_g[lane][7]);
+      s_gc[lane] = by_cls ? gt_cls[gb + g0 + lane] : 0;
+    }
+    __syncthreads();
+    if (lane < rows) {
+      for (int j = 0; j < cn; ++j) {
+        float bev = 0.f, v3 = 0.f;
+        if (!by_cls || s_gc[j] == pc) {
+          const float* B = s_g[j];
+          // one overlap serves both metrics (the clip is ~all of the pair's cost, and two calls are
+          // not merged by the compiler); the BEV ratio is iou_bev()'s, as in nms_mask_rot_kernel
+          const float ov = rotated_overlap(A, B, ca, sa, B[7], B[8]);
+          if (ov > 0.f) {
+            bev = ov / fmaxf(A[3] * A[4] + B[3] * B[4] - ov, 1e-8f);
+            const float h = fmaxf(fminf(ahi, B[2] + 0.5f * B[5]) - fmaxf(alo, B[2] - 0.5f * B[5]), 0.f);
+            const float inter = ov * h;
+            v3 = inter / fmaxf(va + B[3] * B[4] * B[5] - inter, 1e-8f);
+          }
+        }
+        s_bev[lane * kIouLd + j] = bev;
+        s_3d[lane * kIouLd + j] = v3;
+      }
+    }
+    __syncthreads();
+    for (int idx = lane; idx < rows * cn; idx += 64) {
+      const int r = idx / cn, c = idx - r * cn;
+      const long o = obase + (long)r * ng + g0 + c;
+      out_bev[o] = s_bev[r * kIouLd + c];
+      out_3d[o] = s_3d[r * kIouLd + c];
+    }
+    __syncthreads();
+  }
+}
+}  // namespace
+
+// pred [NP, 7] / gt [NG, 7] fp32; pred_cls / gt_cls int32 or both null; pred_off, gt_off, pair_off [F + 1]
+// (pair_off the prefix sum of np_f * ng_f); tile_frame / tile_first [n_tiles]: the frame of each tile of 64
+// predictions and the tile's first prediction within that frame; outputs [total_pairs] fp32.
+TCA_API int tca_box3d_iou(const float* pred, const float* gt, const int* pred_cls, const int* gt_cls,
+                          const int* pred_off, const int* gt_off, const int* pair_off, const int* tile_frame,
+                          const int* tile_first, int n_tiles, long total_pairs, float* iou_bev_out, float* iou_3d_out,
+                          hipStream_t stream) {
+  if (total_pairs < 0 || total_pairs > 2147483647L) return (int)hipErrorInvalidValue;  // offsets are int32
+  if ((pred_cls == nullptr) != (gt_cls == nullptr)) return (int)hipErrorInvalidValue;
+  if (n_tiles <= 0 || total_pairs == 0) return 0;
+  box3d_iou_kernel<<<n_tiles, 64, 0, stream>>>(pred, gt, pred_cls, gt_cls, pred_off, gt_off, pair_off, tile_frame,
+                                               tile_first, iou_bev_out, iou_3d_out);
+  TCA_LAUNCH_CHECK();
+}
+
 // ---- merge-NMS (K4m; reference clients/postprocess/yolov5_postprocess.py:111-117,
 // `merge = True`): every kept box becomes the score-weighted mean of all the
 // image's candidates of its class with IoU > thr (itself included), and with

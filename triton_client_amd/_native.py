@@ -52,6 +52,9 @@ _KERNEL_SIGS = {
     "tca_nms_mask_rot": [P, I, P, P, P, I, I, I, F, I, P, P, P],
     "tca_nms_reduce": [P, P, P, I, I, P, I, P, P, I, I, P, P, P, P, P, P],
     "tca_box_iou": [P, I, P, I, P, P],
+    # pred, gt, pred_cls, gt_cls, pred_off, gt_off, pair_off, tile_frame, tile_first, n_tiles, total_pairs,
+    # iou_bev, iou_3d, stream
+    "tca_box3d_iou": [P, P, P, P, P, P, P, P, P, I, L, P, P, P],
     "tca_nms_merge": [P, P, P, P, P, P, P, P, I, I, I, F, I, I, P, P, P, P, P, P],
     "tca_pc2_unpack": [P, P, P, I, I, I, P, P, I, F, P, I, P, P, P, P],
     "tca_pc2_blocks_per_frame": [I],

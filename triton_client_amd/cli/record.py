@@ -9,6 +9,24 @@ import sys
 import numpy as np
 
 
+GT3D_SIZES = {1: (3.9, 1.6, 1.56), 2: (0.8, 0.6, 1.73), 3: (1.76, 0.6, 1.73)}  # KITTI anchors: Car, Pedestrian, Cyclist
+
+
+def synthetic_gt3d(seq: int) -> dict:
+    """The synthetic 3D ground truth of sweep ``seq`` (a function of ``seq`` alone):
+    1-5 boxes in the sensor frame as an engine-style dict (``pred_boxes`` [n, 7],
+    ``pred_scores`` all 1, ``pred_labels`` 1-3), sizes within 20 % of the KITTI anchors."""
+    rng = np.random.default_rng(1000 + seq)
+    n = int(rng.integers(1, 6))
+    lab = rng.integers(1, 4, n)
+    box = np.zeros((n, 7), np.float64)
+    box[:, 0], box[:, 1] = rng.uniform(5.0, 60.0, n), rng.uniform(-30.0, 30.0, n)
+    box[:, 3:6] = np.array([GT3D_SIZES[int(c)] for c in lab]) * rng.uniform(0.8, 1.2, (n, 3))
+    box[:, 2] = -3.23 + 0.5 * box[:, 5]  # standing on the ground plane of the synthetic sweeps
+    box[:, 6] = rng.uniform(-np.pi, np.pi, n)
+    return {"pred_boxes": box, "pred_scores": np.ones(n, np.float32), "pred_labels": lab.astype(np.int64)}
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description=__doc__)
     p.add_argument("out")
@@ -27,6 +45,8 @@ def main(argv=None) -> int:
     p.add_argument("--rings", type=int, default=64)
     p.add_argument("--columns", type=int, default=1875)
     p.add_argument("--gt", action="store_true", help="also write synthetic ground-truth boxes")
+    p.add_argument("--gt3d-topic", default="/detections_3d_gt",
+                   help="with --lidar --gt: topic of the synthetic 3D ground truth (jsk BoundingBoxArray per sweep)")
     a = p.parse_args(argv)
     from ..inference.ros_inference import detections_to_msg
     from ..ros import Bag, compat, msgs
@@ -69,6 +89,11 @@ def main(argv=None) -> int:
                 raw = np.frombuffer(pts.tobytes(), np.float32).reshape(-1, 4)
                 bag.write(a.lidar_topic, compat.create_cloud_xyzi(raw, msgs.Header(seq=s, stamp=t, frame_id="lidar")),
                           t)
+                if a.gt:
+                    from ..inference.ros_inference3d import boxes_to_jsk
+                    g = synthetic_gt3d(s)
+                    bag.write(a.gt3d_topic, boxes_to_jsk(g, np.arange(len(g["pred_labels"])),
+                                                         msgs.Header(seq=s, stamp=t, frame_id="lidar")), t)
     print(f"wrote {a.frames} frames to {a.out}", file=sys.stderr)
     return 0
 

@@ -313,6 +313,20 @@ def rotated_iou_bev(a, bs) -> np.ndarray:
     return out
 
 
+def rotated_iou_3d(a, bs) -> np.ndarray:
+    """3D IoU of box ``a`` with each of ``bs`` (x, y, z, dx, dy, dz, yaw; z the
+    centre), OpenPCDet ``boxes_iou3d_gpu``: the rotated BEV overlap times the
+    common height, over the union of the volumes."""
+    out = np.zeros(len(bs), np.float64)
+    for k, b in enumerate(np.asarray(bs, np.float64).reshape(-1, len(a)) if len(bs) else ()):
+        h = max(0.0, min(a[2] + a[5] / 2, b[2] + b[5] / 2) - max(a[2] - a[5] / 2, b[2] - b[5] / 2))
+        if h <= 0.0:
+            continue
+        inter = rotated_overlap(a, b) * h
+        out[k] = inter / max(a[3] * a[4] * a[5] + b[3] * b[4] * b[5] - inter, 1e-8)
+    return out
+
+
 # ----------------------------------------------------------------------------- point clouds
 PF_FMT = {1: "b", 2: "B", 3: "h", 4: "H", 5: "i", 6: "I", 7: "f", 8: "d"}
 

@@ -40,15 +40,21 @@ def box_iou(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     return inter / np.maximum(area_a[:, None] + area_b[None, :] - inter, 1e-12)
 
 
-def match_predictions(gt: np.ndarray, pred: np.ndarray, iouv: np.ndarray = IOU_THRESHOLDS) -> np.ndarray:
+def match_predictions(gt: np.ndarray, pred: np.ndarray, iouv: np.ndarray = IOU_THRESHOLDS,
+                      iou: Optional[np.ndarray] = None) -> np.ndarray:
     """gt [M, >=6] (x1,y1,x2,y2,_,cls), pred [N, 6] (x1,y1,x2,y2,conf,cls) →
-    bool correct [N, len(iouv)]."""
+    bool correct [N, len(iouv)].  ``iou`` [M, N]: a precomputed IoU matrix used
+    instead of the axis-aligned one of columns 0-3 (the 3D evaluator's rotated
+    IoU); classes and matching are the same."""
     pred = np.asarray(pred, np.float64).reshape(-1, 6)
     gt = np.asarray(gt, np.float64).reshape(-1, gt.shape[-1] if np.ndim(gt) == 2 and len(gt) else 6)
     correct = np.zeros((len(pred), len(iouv)), bool)
     if len(pred) == 0 or len(gt) == 0:
         return correct
-    iou = box_iou(gt[:, :4], pred[:, :4])
+    if iou is None:
+        iou = box_iou(gt[:, :4], pred[:, :4])
+    else:
+        iou = np.asarray(iou, np.float64).reshape(len(gt), len(pred))
     li, di = np.nonzero((iou >= iouv[0]) & (gt[:, 5:6] == pred[None, :, 5]))
     if len(li):
         m = np.stack([li, di, iou[li, di]], 1)
@@ -188,10 +194,18 @@ class EvalSummary:
     classes: np.ndarray
     images: int
     matched_images: int
+    iouv: Optional[np.ndarray] = None  # the thresholds of ap's columns (None: IOU_THRESHOLDS)
 
     @property
     def map50(self) -> float:
         return float(self.ap[:, 0].mean()) if len(self.ap) else 0.0
+
+    @property
+    def map_by_iou(self) -> Dict[float, float]:
+        """Class-mean AP at each IoU threshold of this summary: {threshold: mAP}
+        (``map50`` is the first column, whatever its threshold)."""
+        iouv = IOU_THRESHOLDS if self.iouv is None else self.iouv
+        return {float(round(t, 6)): float(self.ap[:, k].mean()) if len(self.ap) else 0.0 for k, t in enumerate(iouv)}
 
     @property
     def map(self) -> float:
@@ -243,3 +257,109 @@ class DetectionEvaluator:
         tp, conf, pc, tc = self.stats()
         p, r, ap, f1, cls = ap_per_class(tp, conf, pc, tc)
         return EvalSummary(p, r, ap, f1, cls, len(set(self.preds) | set(self.gts)), len(self.matched()))
+
+
+IOU_THRESHOLDS_3D = (0.25, 0.5, 0.7)
+
+
+@dataclass
+class EvalSummary3D(EvalSummary):
+    """:class:`EvalSummary` of a 3D run.  ``ap`` has one column per threshold of
+    ``iouv``; precision / recall / F1 are read at the lowest one."""
+    metric: str = "bev"
+
+    def as_dict(self, names: Optional[Sequence[str]] = None, label_base: int = 1) -> dict:
+        """``names[label - label_base]`` names a class (the anchor detectors' labels are
+        1-based, CenterPoint's 0-based)."""
+        keys = [f"{t:g}" for t in self.iouv]
+        per = {}
+        for i, c in enumerate(self.classes):
+            k = int(c) - label_base
+            key = names[k] if names is not None and 0 <= k < len(names) else str(int(c))
+            per[key] = {"p": float(self.precision[i]), "r": float(self.recall[i]), "f1": float(self.f1[i]),
+                        "ap": {t: float(v) for t, v in zip(keys, self.ap[i])}}
+        return {"images": self.images, "matched_images": self.matched_images, "metric": self.metric,
+                "iou_thresholds": [float(t) for t in self.iouv],
+                "map": {t: v for t, v in zip(keys, self.map_by_iou.values())}, "per_class": per}
+
+
+@dataclass
+class DetectionEvaluator3D:
+    """The 3D counterpart of :class:`DetectionEvaluator`: per-frame predictions
+    ``[n, 9]`` (x, y, z, dx, dy, dz, yaw, score, cls) and ground truth ``[m, 8]``
+    (…, yaw, cls), joined by frame id.  A prediction is correct at a threshold
+    when its rotated IoU (``metric`` ``"bev"`` or ``"3d"``) with a same-class
+    ground-truth box reaches it; matching is :func:`match_predictions`'.  The IoU
+    of every matched frame comes from one :func:`..ops.box3d.box3d_iou_ragged`
+    call (one kernel launch on a GPU), the matching runs per frame on the host."""
+
+    metric: str = "bev"
+    iouv: np.ndarray = field(default_factory=lambda: np.asarray(IOU_THRESHOLDS_3D, np.float64))
+    device: object = "auto"
+    preds: Dict[int, np.ndarray] = field(default_factory=dict)
+    gts: Dict[int, np.ndarray] = field(default_factory=dict)
+
+    def __post_init__(self):
+        if self.metric not in ("bev", "3d"):
+            raise ValueError(f"metric {self.metric!r}: 'bev' or '3d'")
+        self.iouv = np.asarray(self.iouv, np.float64).reshape(-1)
+        if len(self.iouv) == 0 or (np.diff(self.iouv) <= 0).any():
+            raise ValueError("iouv: ascending IoU thresholds")
+
+    def add_prediction(self, seq: int, dets: np.ndarray) -> None:
+        self.preds[int(seq)] = np.asarray(dets, np.float64).reshape(-1, 9)
+
+    def add_detections(self, seq: int, pred: dict, conf_thres: float = 0.0) -> None:
+        """An engine result (``pred_boxes`` [n, 7] or CenterPoint's [n, 9] with yaw
+        at index 8, ``pred_scores``, ``pred_labels``), kept from ``conf_thres`` up."""
+        from ..ops.box3d import boxes7
+
+        s = np.asarray(pred["pred_scores"], np.float64).reshape(-1)
+        b = np.asarray(pred["pred_boxes"], np.float64)
+        b = boxes7(b.reshape(len(s), -1)) if len(s) else np.zeros((0, 7))
+        d = np.concatenate([b, s[:, None], np.asarray(pred["pred_labels"], np.float64).reshape(-1, 1)], 1)
+        self.add_prediction(seq, d[s >= conf_thres])
+
+    def add_ground_truth(self, seq: int, gt: np.ndarray) -> None:
+        self.gts[int(seq)] = np.asarray(gt, np.float64).reshape(-1, 8)
+
+    def matched(self) -> List[int]:
+        return sorted(set(self.preds) & set(self.gts))
+
+    def ious(self):
+        """→ (frames, iou, pair_off): the chosen metric's IoU of every matched
+        frame, frame k's [n_pred, n_gt] block at ``pair_off[k]``."""
+        from ..ops.box3d import box3d_iou_ragged, ragged_offsets
+
+        frames = self.matched()
+        P = [self.preds[s] for s in frames]
+        G = [self.gts[s] for s in frames]
+        poff, goff, _ = ragged_offsets([len(p) for p in P], [len(g) for g in G])
+        pa = np.concatenate(P) if P else np.zeros((0, 9))
+        ga = np.concatenate(G) if G else np.zeros((0, 8))
+        bev, v3, pair_off = box3d_iou_ragged(pa[:, :7], ga[:, :7], poff, goff, pa[:, 8], ga[:, 7], device=self.device)
+        return frames, (bev if self.metric == "bev" else v3), pair_off
+
+    def stats(self, ious=None):
+        """``ious``: a precomputed :meth:`ious` result (default: computed here)."""
+        frames, iou, off = self.ious() if ious is None else ious
+        tp, conf, pc, tc = [], [], [], []
+        for k, s in enumerate(frames):
+            p, g = self.preds[s], self.gts[s]
+            p6, g6 = np.zeros((len(p), 6)), np.zeros((len(g), 6))
+            p6[:, 4], p6[:, 5], g6[:, 5] = p[:, 7], p[:, 8], g[:, 7]
+            m = np.asarray(iou[off[k]:off[k + 1]], np.float64).reshape(len(p), len(g)).T
+            tp.append(match_predictions(g6, p6, self.iouv, iou=m))
+            conf.append(p[:, 7])
+            pc.append(p[:, 8])
+            tc.append(g[:, 7])
+        if not tp:
+            z = np.zeros((0,))
+            return np.zeros((0, len(self.iouv)), bool), z, z, z
+        return np.concatenate(tp), np.concatenate(conf), np.concatenate(pc), np.concatenate(tc)
+
+    def summary(self, ious=None) -> EvalSummary3D:
+        tp, conf, pc, tc = self.stats(ious)
+        p, r, ap, f1, cls = ap_per_class(tp, conf, pc, tc)
+        return EvalSummary3D(p, r, ap, f1, cls, len(set(self.preds) | set(self.gts)), len(self.matched()),
+                             self.iouv.copy(), self.metric)
