@@ -30,12 +30,9 @@
 // step).  Each stage also carries the step's 128 deconv biases (so the K loop
 // issues no ordinary global load, which would make hipcc drain the DMA queue);
 // head weights and bias are loaded once per workgroup and stay in LDS.
-#include "tca_common.h"
+#include "tca_mfma.h"
 
 using namespace tca;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -66,19 +63,9 @@ struct NeckArgs {
   int B, H, W, S, nbr, nsteps, ntiles;
 };
 
-__device__ uint4 g_neck_zero_page[64];
+__device__ uint4 g_neck_zero_page[64];  // this file's own zero page: 1 KiB of zeros for the glds16 tails
 
-typedef __attribute__((address_space(3))) void* lds_void_t;
-typedef __attribute__((address_space(1))) void* gbl_void_t;
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* l) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t)g, (lds_void_t)l, 16, 0, 0);
-}
-
-__device__ __forceinline__ void wait_vmcnt0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
-
-__device__ __forceinline__ int swz2(int row) { return (row >> 1) & 7; }
-
+// local on purpose: the bf16 neck's accumulator pair -> one fragment of the head GEMM
 __device__ __forceinline__ bf16x8 pack8(const f32x4& lo, const f32x4& hi) {
   bf16x8 v;
   v[0] = (__bf16)lo[0]; v[1] = (__bf16)lo[1]; v[2] = (__bf16)lo[2]; v[3] = (__bf16)lo[3];
@@ -188,7 +175,7 @@ __global__ void __launch_bounds__(NT) bev_neck_head_kernel(NeckArgs a) {
   Tile ct = tile_of(a.S, t_lo + slot, nqt);
   for (int g = 0; g < total; ++g) {
     const int cur = g & 1;
-    wait_vmcnt0();
+    wait_vm<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // stage g landed for every wave; every wave is done with g-1's buffer
     asm volatile("" ::: "memory");
@@ -283,7 +270,7 @@ __global__ void __launch_bounds__(NT) bev_neck_head_kernel(NeckArgs a) {
     ++c_k;
     ct = tile_of(a.S, t_lo + slot + c_k * nslot, nqt);
   }
-  wait_vmcnt0();  // no LDS DMA may outlive the workgroup (a tile-less workgroup still loaded the head)
+  wait_vm<0>();  // no LDS DMA may outlive the workgroup (a tile-less workgroup still loaded the head)
 }
 
 // ============================================================================
@@ -333,49 +320,16 @@ constexpr int Y_HEAD_STEPS = CB / 64;  // head steps per branch (64 channels eac
 
 template <int V> struct IC { static constexpr int value = V; };
 
-// 16-row periodic slot swizzle: conv_mfma.hip's swz3 on the row's position in
-// its 16-row fragment (conflict-free for the b128 fragment reads at any 16-row
-// base), so the fragment-read address is a per-lane base plus a constant per
-// fragment (folded into the ds_read offset instead of one VGPR per fragment)
-__device__ __forceinline__ int swz3(int row) { return ((row & 15) ^ ((row & 15) >> 3)) & 7; }
+// The fp32 neck's LDS rows use the 16-row periodic slot swizzle of the xb tiles (swzp in
+// tca_mfma.h), so the fragment-read address is a per-lane base plus a constant per fragment
+// (folded into the ds_read offset instead of one VGPR per fragment).
 
-__device__ __forceinline__ void split8(const float4& x0, const float4& x1, bf16x8& hi, bf16x8& lo) {
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const __bf16 h = (__bf16)v[e];
-    hi[e] = h;
-    lo[e] = (__bf16)(v[e] - (float)h);
-  }
-}
-
+// local on purpose (the neck's relu, instead of act_fn's fmaxf):
 // max(x, 0) as ONE v_max_i32 on the bits (a negative float is a negative int; -0 -> +0): fmaxf in
 // IEEE mode costs a canonicalizing v_max_f32 per input on top of the max
 __device__ __forceinline__ float relu_bits(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 
-__device__ __forceinline__ void mfma3(f32x4& acc, const bf16x8& bh, const bf16x8& bl, const bf16x8& ah,
-                                      const bf16x8& al) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, acc, 0, 0, 0);
-}
-
-constexpr unsigned kOutOfRange = 0x80000000u;  // >= any num_records the launcher accepts (< 2^31): reads zeros
-
-// one 16-B-per-lane LDS DMA through a buffer resource: voffset per lane, soffset scalar
-__device__ __forceinline__ void bdma16(unsigned voff, __amdgpu_buffer_rsrc_t rsrc, const void* l, unsigned soff) {
-  const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)l);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(dst), "s"(soff)
-               : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
-}
+// local on purpose: wait_vm for a run-time count, over the counts this kernel can have in flight;
 // all but this wave's n youngest vector-memory ops done (n = the DMA pieces of
 // the one step allowed to stay in flight; an unlisted n waits for everything)
 template <typename T>
@@ -465,13 +419,13 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) bev_neck_head_x3_k
       const int yg = r_yx[j] >> 16, x = r_yx[j] & 0xFFFF;
       a_vo[j] = r_yx[j] < 0 ? kOutOfRange
                             : (unsigned)((((yg * f + sy) * Wi + x * f + sx) * ldx + a.offx[i_br] +
-                                          (lslot ^ swz3(row)) * 4) * 4);
+                                          (lslot ^ swzp(row)) * 4) * 4);
     }
     const int sub = (i_cy % s) * s + (i_cx % s);
 #pragma unroll
     for (int j = 0; j < Y_B_INS; ++j) {
       const int row = (wid * Y_B_INS + j) * 8 + lrow;
-      b_vo[j] = (unsigned)(((sub * CB + row) * 2 * cin + (lslot ^ swz3(row)) * 8) * 2);
+      b_vo[j] = (unsigned)(((sub * CB + row) * 2 * cin + (lslot ^ swzp(row)) * 8) * 2);
     }
     bias_vo = (unsigned)((sub * CB + wid * (4 * T::BIAS_LANES) + lane * 4) * 4);
   };
@@ -483,7 +437,7 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) bev_neck_head_x3_k
   for (int k = 0; k < HP_MAX; ++k) {
     const int p = wid + k * NW;
     const int c = p / (NH / 8), r8 = p - c * (NH / 8), h = r8 * 8 + lrow;
-    h_vo[k] = (unsigned)((h * ldwh + c * 64 + (lslot ^ swz3(h)) * 8) * 2);
+    h_vo[k] = (unsigned)((h * ldwh + c * 64 + (lslot ^ swzp(h)) * 8) * 2);
     h_lds[k] = p < Y_HEAD_PIECES ? c * NH * X_ROWB + r8 * 1024 : -1;
   }
   const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.wh, (short)0, NH * ldwh * 2, 0x00020000);
@@ -572,8 +526,8 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) bev_neck_head_x3_k
 #pragma unroll
     for (int u = 0; u < NH / 16; ++u) {
       const int h = u * 16 + fr;
-      const bf16x8 wh_ = *reinterpret_cast<const bf16x8*>(whb + h * X_ROWB + (((2 * fq) ^ swz3(h)) << 4));
-      const bf16x8 wl_ = *reinterpret_cast<const bf16x8*>(whb + h * X_ROWB + (((2 * fq + 1) ^ swz3(h)) << 4));
+      const bf16x8 wh_ = *reinterpret_cast<const bf16x8*>(whb + h * X_ROWB + (((2 * fq) ^ swzp(h)) << 4));
+      const bf16x8 wl_ = *reinterpret_cast<const bf16x8*>(whb + h * X_ROWB + (((2 * fq + 1) ^ swzp(h)) << 4));
 #pragma unroll
       for (int i = 0; i < Y_FM; ++i) mfma3(acc2[i][u], wh_, wl_, xh[i], xl[i]);
     }
@@ -599,11 +553,11 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) bev_neck_head_x3_k
         for (int i = 0; i < Y_FM; ++i) {
           const int r = wid * 16 * Y_FM + i * 16 + fr;
           if constexpr (PAIR) {
-            ah[i] = *reinterpret_cast<const bf16x8*>(sa + r * X_ROWB + (((2 * fq) ^ swz3(r)) << 4));
-            al[i] = *reinterpret_cast<const bf16x8*>(sa + r * X_ROWB + (((2 * fq + 1) ^ swz3(r)) << 4));
+            ah[i] = *reinterpret_cast<const bf16x8*>(sa + r * X_ROWB + (((2 * fq) ^ swzp(r)) << 4));
+            al[i] = *reinterpret_cast<const bf16x8*>(sa + r * X_ROWB + (((2 * fq + 1) ^ swzp(r)) << 4));
           } else {
-            const float4 x0 = *reinterpret_cast<const float4*>(sa + r * X_ROWB + (((2 * fq) ^ swz3(r)) << 4));
-            const float4 x1 = *reinterpret_cast<const float4*>(sa + r * X_ROWB + (((2 * fq + 1) ^ swz3(r)) << 4));
+            const float4 x0 = *reinterpret_cast<const float4*>(sa + r * X_ROWB + (((2 * fq) ^ swzp(r)) << 4));
+            const float4 x1 = *reinterpret_cast<const float4*>(sa + r * X_ROWB + (((2 * fq + 1) ^ swzp(r)) << 4));
             split8(x0, x1, ah[i], al[i]);
           }
         }
@@ -616,8 +570,8 @@ __global__ void __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) bev_neck_head_x3_k
 #pragma unroll
           for (int jj = 0; jj < JB; ++jj) {
             const int r = (jh * JB + jj) * 16 + fr;
-            wh_[jj] = *reinterpret_cast<const bf16x8*>(sb + r * X_ROWB + (((2 * fq) ^ swz3(r)) << 4));
-            wl_[jj] = *reinterpret_cast<const bf16x8*>(sb + r * X_ROWB + (((2 * fq + 1) ^ swz3(r)) << 4));
+            wh_[jj] = *reinterpret_cast<const bf16x8*>(sb + r * X_ROWB + (((2 * fq) ^ swzp(r)) << 4));
+            wl_[jj] = *reinterpret_cast<const bf16x8*>(sb + r * X_ROWB + (((2 * fq + 1) ^ swzp(r)) << 4));
           }
 #pragma unroll
           for (int jj = 0; jj < JB; ++jj)

@@ -25,12 +25,9 @@
 // (frame, task) segment with a (score, ~pixel) key, so the following top-k /
 // rotated NMS (nms.hip, segments = frame x task) is deterministic.  Box layout
 // [x, y, z, w, l, h, yaw, vx, vy] keeps the NMS fields at 0..6.
-#include "tca_common.h"
+#include "tca_mfma.h"
 
 using namespace tca;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -38,11 +35,6 @@ struct PfnGeom {
   float r0, r1, vx, vy;
   int nx, ny;
 };
-
-__device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
-  hi = (__bf16)v;
-  lo = (__bf16)(v - (float)hi);
-}
 
 template <bool FROM_SLOTS, bool F32>
 __global__ void __launch_bounds__(256) pfn2_kernel(

@@ -3,14 +3,13 @@
 // (data/pointpillar.yaml:64-70 BaseBEVBackbone, run by
 // examples/pointpillar_kitti/1/model.py:163): pair activations in and out,
 // split-product MFMA (bf16 x3, fp32 accumulation; see conv_mfma.hip "fp32 mode").
-#include "tca_common.h"
+#include "tca_mfma.h"
 
 #include <cstdlib>
 
-namespace {
+using namespace tca;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+namespace {
 
 struct Hx3Args {
   const float* in_f;   // pair storage [B, H, W, ldi], channels [ci_off, ci_off + Cin)
@@ -30,50 +29,8 @@ struct Hx3Args {
   int uni_min;
 };
 
-constexpr unsigned kOutOfRange = 0x80000000u;  // buffer offset past any num_records (< 2^31): reads zeros
-
-__device__ __forceinline__ float act_fn(float v, int act) {
-  switch (act) {
-    case 1: return fmaxf(v, 0.f);
-    case 2: return v / (1.f + __expf(-v));
-    case 3: return v > 0.f ? v : 0.1f * v;
-    default: return v;
-  }
-}
-
-// slot swizzle of halo position hx (0..17), as conv_mfma.hip hx: conflict-free b128
-// fragment reads at the three tap shifts
-__device__ __forceinline__ int hswz(int hx) { return (0xb29108 >> (3 * (hx >> 1))) & 7; }
-
-// x * w ~= xh*wh + xh*wl + xl*wh on the bf16 MFMA (fp32 accumulate), same order as conv_mfma.hip.
-// (The kernels below issue these three products product-major over their accumulators.)
-[[maybe_unused]] __device__ __forceinline__ void mfma3(f32x4& acc, const bf16x8& bh, const bf16x8& bl, const bf16x8& ah,
-                                      const bf16x8& al) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, acc, 0, 0, 0);
-}
-
-__device__ __forceinline__ void pair_split8(const float* v, uint4& hi, uint4& lo) {
-  __bf16 h[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = (__bf16)v[e];
-    l[e] = (__bf16)(v[e] - (float)h[e]);
-  }
-  hi = *reinterpret_cast<const uint4*>(h);
-  lo = *reinterpret_cast<const uint4*>(l);
-}
-
-__device__ __forceinline__ void pair_join8(const float* p, float* v) {
-  const uint4 hq = *reinterpret_cast<const uint4*>(p);
-  const uint4 lq = *reinterpret_cast<const uint4*>(p + 4);
-  const __bf16* h = reinterpret_cast<const __bf16*>(&hq);
-  const __bf16* l = reinterpret_cast<const __bf16*>(&lq);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (float)h[e] + (float)l[e];
-}
-
+// x * w ~= xh*wh + xh*wl + xl*wh on the bf16 MFMA (fp32 accumulate): the kernels below issue
+// tca_mfma.h mfma3's three products product-major over their accumulators, in its order.
 // epilogue: bias + act from the accumulators into an fp32 LDS tile (tile row ml = line * 16 +
 // position along the fragment axis), then 16-B pair stores (+ residual).  The tile rows are
 // BN floats with the 16-B quads XOR-swizzled by the row (quad q of row ml at q ^ (ml & 15)):

@@ -20,12 +20,11 @@
 //      without an occupied input gets act(bias): the dense kernel's value there, bit for bit).
 // The MFMA work is ~2.25 x (occupied cells) 16-row fragments instead of 9 x (output pixels);
 // the kernel is bound by its dense output stores.
-#include "tca_common.h"
+#include "tca_mfma.h"
+
+using namespace tca;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct S2spArgs {
   const float* in;           // pair storage [B, H, W, ldi], channels [ci_off, ci_off + Cin)
@@ -39,15 +38,6 @@ struct S2spArgs {
 };
 
 constexpr int TW = 32, N = 64, LDA = N + 4;
-
-__device__ __forceinline__ float act_fn(float v, int act) {
-  switch (act) {
-    case 1: return fmaxf(v, 0.f);
-    case 2: return v / (1.f + __expf(-v));
-    case 3: return v > 0.f ? v : 0.1f * v;
-    default: return v;
-  }
-}
 
 // TH = 8: 256 pixels, one per thread (78 KiB LDS, two workgroups per CU); TH = 4: 128 pixels
 // (40 KiB, four per CU); TH = 2: 64 pixels (20 KiB, eight per CU)
@@ -141,7 +131,7 @@ __global__ void __launch_bounds__(256) conv_s2sp_kernel(S2spArgs a) {
     if (tn < 9) load(tn, cn, nxt);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) {  // products in conv_hx3.hip mfma3's order
+    for (int kc = 0; kc < KC; ++kc) {  // products in mfma3's order
       const bf16x8 ah = *reinterpret_cast<const bf16x8*>(&cur.xh[kc]);
       const bf16x8 al = *reinterpret_cast<const bf16x8*>(&cur.xl[kc]);
       const bf16x8 bh = *reinterpret_cast<const bf16x8*>(&cur.wh[kc]);

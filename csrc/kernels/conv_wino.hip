@@ -24,15 +24,13 @@
 // The raw halo of chunk c + 1 lands by LDS DMA during chunk c's MFMAs; its transform runs between
 // chunks (one image, two workgroups per CU, so one's transform overlaps the other's MFMAs).  Epilogue: y0 = m0 + m1 + m2, y1 = m1 - m2 - m3 per lane (the lane
 // holds all four positions of its tile), bias + act, an LDS staging tile, 16-B stores.
-#include "tca_common.h"
+#include "tca_mfma.h"
+
+using namespace tca;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOutOfRange = 0x80000000u;  // buffer offset past any num_records (< 2^31): reads zeros
 
 struct WinoArgs {
   const float* in_f;  // [B, H, W, ldi] pair or fp32 storage, channels [ci_off, ci_off + Cin)
@@ -58,12 +56,13 @@ __device__ __forceinline__ float fadd1(float x, float y) {
   asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
   return r;
 }
-__device__ __forceinline__ float fsub1(float x, float y) {
+__device__ __forceinline__ float fsub1(float x, float y) {  // (split8 below uses it: its one difference from pair_split8)
   float r;
   asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
   return r;
 }
 
+// local on purpose: tca_mfma.h pair_split8 with the subtract pinned to the unpacked fsub1
 __device__ __forceinline__ void split8(const float* v, u32x4& hi, u32x4& lo) {
   __bf16 h[8], l[8];
 #pragma unroll
@@ -75,7 +74,8 @@ __device__ __forceinline__ void split8(const float* v, u32x4& hi, u32x4& lo) {
   lo = *reinterpret_cast<const u32x4*>(l);
 }
 
-// 8 channels of one input pixel as fp32: pair storage (8 hi bf16 | 8 lo bf16) or fp32 (two quads)
+// 8 channels of one input pixel as fp32: pair storage (8 hi bf16 | 8 lo bf16) or fp32 (two quads);
+// local on purpose: pair_join8's sums on registers already loaded, with the fp32 form beside it
 template <bool PIN>
 __device__ __forceinline__ void join8(const u32x4& p0, const u32x4& p1, float* d) {
   if constexpr (PIN) {
@@ -95,22 +95,6 @@ __device__ __forceinline__ void join8(const u32x4& p0, const u32x4& p1, float* d
 
 template <int P> struct PosC { static constexpr int value = P; };
 
-// one 16-B-per-lane LDS DMA through a buffer resource: voffset per lane, soffset scalar; the wave's
-// 64 pieces land contiguously at the wave-uniform LDS address l (lane i at l + 16 i)
-__device__ __forceinline__ void bdma16(unsigned voff, __amdgpu_buffer_rsrc_t rsrc, const void* l, unsigned soff) {
-  const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)l);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(dst), "s"(soff)
-               : "memory");
-}
-
-__device__ __forceinline__ void wait_vmcnt0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
-template <int N>
-__device__ __forceinline__ void wait_vm() {  // at most this wave's N youngest vector-memory ops in flight
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
-}
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -312,7 +296,7 @@ __global__ void __launch_bounds__(WN * 64, 2) conv_wino_kernel(WinoArgs a) {
   raw_dma(0);
   wload(0, w[0]);
   wload(1, w[1]);
-  wait_vmcnt0();
+  wait_vm<0>();
   lds_barrier();
   transform();
   lds_barrier();  // the image is visible and every wave is done with the raw halo
@@ -332,7 +316,7 @@ __global__ void __launch_bounds__(WN * 64, 2) conv_wino_kernel(WinoArgs a) {
       if (c + 2 < nc) raw_dma(c + 2);
     }
   }
-  wait_vmcnt0();  // the clamped tail prefetches
+  wait_vm<0>();  // the clamped tail prefetches
   lds_barrier();  // the epilogue reuses the image
 
   // ---- epilogue: output transform + bias + act -> fp32 staging tile [TH * 32 rows][BN] (16-B

@@ -25,12 +25,9 @@
 // so the 27 MB/frame canvas is never memset.
 #include <type_traits>
 
-#include "tca_common.h"
+#include "tca_mfma.h"
 
 using namespace tca;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -38,11 +35,6 @@ struct PillarGeom {
   float r0, r1, r2, vx, vy, vz;
   int nx, ny;
 };
-
-__device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
-  hi = (__bf16)v;
-  lo = (__bf16)(v - (float)hi);
-}
 
 template <bool FROM_SLOTS, typename CT, int PFIX = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) pillar_vfe_kernel(

@@ -22,12 +22,9 @@
 // epilogue scatters straight into the NHWC BEV map (HeightCompression) at
 // channel z*Cout + c (the 2D backbone's first conv is permuted to match), so
 // the dense [B, C, D, H, W] tensor never exists.
-#include "tca_common.h"
+#include "tca_mfma.h"
 
 using namespace tca;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -276,10 +273,6 @@ struct SpGemmArgs {
   int act;                   // 0 none, 1 relu
 };
 
-// 16-B chunk c (0..3) of row r in a [rows][64 B] tile, XOR-swizzled so the
-// ds_read_b128 fragment reads are bank-conflict free.
-__device__ __forceinline__ int swz(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
-
 template <int BM, int BN, int WM, int WN>
 __global__ void __launch_bounds__(256) sp_gemm_kernel(SpGemmArgs a) {
   static_assert(WM * WN == 4 && BM == 64, "4 waves, one tap-mask word per tile");
@@ -463,16 +456,6 @@ struct SpGemmX3Args {
 // 16-B chunk c (0..7) of row r in a [rows][128 B] tile (conflict-free b128 reads)
 __device__ __forceinline__ int swz8(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
-__device__ __forceinline__ void split8f(const float4& x0, const float4& x1, bf16x8& h, bf16x8& l) {
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const __bf16 hi = (__bf16)v[k];
-    h[k] = hi;
-    l[k] = (__bf16)(v[k] - (float)hi);
-  }
-}
-
 template <int BM, int BN, int WM, int WN>
 __global__ void __launch_bounds__(256) sp_gemm_x3_kernel(SpGemmX3Args a) {
   static_assert(WM * WN == 4 && BM == 64, "4 waves, one tap-mask word per tile");
@@ -579,7 +562,7 @@ __global__ void __launch_bounds__(256) sp_gemm_x3_kernel(SpGemmX3Args a) {
         const int r = wm * TM + x * 16 + fr;
         const float4 x0 = *reinterpret_cast<const float4*>(sa + swz8(r, 2 * fq));
         const float4 x1 = *reinterpret_cast<const float4*>(sa + swz8(r, 2 * fq + 1));
-        split8f(x0, x1, ah[x], al[x]);
+        split8(x0, x1, ah[x], al[x]);
       }
 #pragma unroll
       for (int y = 0; y < FN; ++y) {
