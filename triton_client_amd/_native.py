@@ -32,6 +32,9 @@ _KERNEL_SIGS = {
     # JPEG pixel reconstruction (csrc/kernels/jpeg.hip)
     "tca_jpeg_idct": [P, P, P, P, L, L, I, P],
     "tca_jpeg_color": [P, P, P, L, L, I, P],
+    # src, src frame stride, step, H, W, code, is_bigendian, dst, dst frame stride, n, stream
+    # (csrc/kernels/encodings.hip)
+    "tca_image_to_rgb8": [P, L, I, I, I, I, I, P, L, I, P],
     "tca_image_preprocess": [P, L, I, I, I, I, I, P, I, I, I, I, I, I, I, I, I, I, F, I, F, F, F, F, F, F, P],
     # src, batch stride, src_h, src_w, row stride, src_c, swap_rb, dst_h, dst_w, B, top, left, reg_h, reg_w, pad,
     # quantize, sc0-2, b0-2, w0, bias0, act0, w1, bias1, act1, out, ldo, co_off, stream

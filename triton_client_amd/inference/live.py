@@ -13,8 +13,12 @@ camera (:class:`LiveCamera`)
     host threads, no GIL) straight into a pinned slot -> H2D -> HIP IDCT +
     colour (``csrc/kernels/jpeg.hip``) into the pipeline's frame buffer.  Raw
     ``Image`` rgb8: the rows are gathered into the pinned slot by C++ threads
-    (``csrc/runtime/host_copy.cpp``).  Then the captured YOLOv5 / YOLOv4 /
-    Detectron step, and boxes + labels drawn on the resident frames
+    (``csrc/runtime/host_copy.cpp``).  Every other raw ``Image`` encoding (bgr8 /
+    rgba8 / bgra8, mono8 / mono16, YUV 4:2:2, 8-bit Bayer, rgb8 with padded rows):
+    the payload as the sensor sent it is gathered into the pinned slot -> H2D ->
+    HIP conversion to rgb8 (``csrc/kernels/encodings.hip``) into the frame buffer
+    (``TCA_DEVICE_ENCODINGS=0``: converted on the host instead).  Then the
+    captured YOLOv5 / YOLOv4 / Detectron step, and boxes + labels drawn on the resident frames
     (``csrc/kernels/draw.hip``); the annotated frames and the detections come
     back in one D2H into pinned memory that the published ``Image`` wraps
     without a copy.
@@ -41,6 +45,8 @@ import numpy as np
 import torch
 
 from .. import _native
+from ..ops import golden
+from ..ops.image import image_frame_bytes, image_to_rgb8
 from ..ops.jpeg import GEOM_FIELDS, JpegGeometry, decode_pil, probe
 from ..pipelines.stream import PinnedSlots, StreamExecutor
 from ..ros import msgs
@@ -81,18 +87,29 @@ class _CameraEngine:
     """One frame geometry + input kind: a calibrated pipeline, its two captured
     graphs and a pool of pinned staging slots."""
 
-    def __init__(self, live: "LiveCamera", kind: str, hw: Tuple[int, int], geo: Optional[JpegGeometry],
-                 draw: bool, names: Tuple[str, ...], sample: np.ndarray):
+    def __init__(self, live: "LiveCamera", kind: str, hw: Tuple[int, int], geo, draw: bool, names: Tuple[str, ...],
+                 sample: np.ndarray):
+        """geo: the :class:`JpegGeometry` of a ``"jpeg"`` engine, (encoding, step, is_bigendian)
+        of a ``"raw"`` one, else None."""
         det = live.det
-        self.live, self.kind, self.hw, self.geo, self.draw = live, kind, hw, geo, draw
+        self.live, self.kind, self.hw, self.draw = live, kind, hw, draw
+        raw = geo if kind == "raw" else None
+        self.geo = geo = geo if kind == "jpeg" else None
         self.B, dev = det.B, det.device
+        H, W = hw
+        if raw is not None:
+            self.enc, self.step, self.be = raw
+            self.raw_bytes = image_frame_bytes(H, W, self.step, self.enc)  # ValueError: a geometry it refuses
+            self.raw_stride = (self.raw_bytes + 15) // 16 * 16
         self.p = det._calibrated_pipeline(hw, sample)
         self.names_dev = None
         if draw and names:
             from ..utils.draw import names_table
             self.names_dev = torch.from_numpy(names_table(names)).to(dev)
         self.ex = StreamExecutor(self._step, [(self.p, "frames")], dev, graph=det.graph)
-        H, W = hw
+        if raw is not None:
+            self.raw_dev = [torch.empty((self.B, self.raw_stride), dtype=torch.uint8, device=dev)
+                            for _ in range(self.ex.sets)]
         if geo is not None:
             self.geom_rec = np.array([geo.width, geo.height, geo.nc, geo.hmax, geo.vmax, geo.mcux, geo.mcuy,
                                       *[v for hv in geo.sampling for v in hv], geo.nblocks, 0, 0], np.int32)
@@ -102,6 +119,8 @@ class _CameraEngine:
             self.planes = torch.empty((self.B, geo.plane_bytes), dtype=torch.uint8, device=dev)
 
         def make_slot():
+            if raw is not None:  # the payloads as the sensor sent them
+                return SimpleNamespace(raw=torch.empty((self.B, self.raw_stride), dtype=torch.uint8).pin_memory())
             s = SimpleNamespace(frames=torch.empty((self.B, H, W, 3), dtype=torch.uint8).pin_memory())
             s.frames_np = s.frames.numpy()
             if geo is not None:
@@ -150,6 +169,10 @@ class _CameraEngine:
         gather_copy([s.frames.data_ptr() + i * frame for i in direct], srcs, [frame] * len(direct),
                     self.live.threads)
 
+    def _stage_raw(self, s, batch: Sequence) -> None:
+        gather_copy([s.raw.data_ptr() + i * self.raw_stride for i in range(len(batch))], [m.data for m in batch],
+                    [self.raw_bytes] * len(batch), self.live.threads)
+
     # ------------------------------------------------------------------ one batch
     def submit(self, batch: Sequence, out_frames: Optional[Sequence[torch.Tensor]] = None):
         """Stage ``batch`` (<= B messages of this engine's kind and geometry) and
@@ -159,15 +182,30 @@ class _CameraEngine:
         n = len(batch)
         if not 0 < n <= self.B:
             raise ValueError(f"{n} frames for a batch of {self.B}")
+        if self.kind == "raw":
+            for m in batch:  # a short payload: the host path's ValueError, before anything is staged
+                if len(m.data) < self.raw_bytes:
+                    self.live.host_rgb(m, self.hw)
+                    raise ValueError(f"{self.enc!r} image: {len(m.data)} B of data, {self.raw_bytes} B needed")
         s = self.slots.acquire()
         ticket = None
         try:
             fb: List[int] = []
             if self.kind == "jpeg":
                 fb = self._stage_jpeg(s, [m.data for m in batch])
+            elif self.kind == "raw":
+                self._stage_raw(s, batch)
             else:
                 self._stage_frames(s, batch)
-            if self.kind == "jpeg":
+            if self.kind == "raw":
+                def copies(k):
+                    return [(self.raw_dev[k], s.raw[:n])]
+
+                def pre(k):
+                    H, W = self.hw
+                    image_to_rgb8(self.raw_dev[k], H, W, self.step, self.enc, self.be, out=self.ex.inputs[k][0], n=n,
+                                  stream=torch.cuda.current_stream())
+            elif self.kind == "jpeg":
                 def copies(k):
                     return [(self.coef_dev[k], s.coef[:n]), (self.q_dev[k], s.q[:n])]
 
@@ -238,7 +276,8 @@ class LiveCamera:
     @staticmethod
     def host_rgb(msg_or_data, hw: Optional[Tuple[int, int]] = None) -> np.ndarray:
         """Host decode for what the device path does not take (progressive JPEG, PNG, JPEGs
-        the entropy decoder rejects, and every raw ``Image`` that is not packed rgb8: bgr8 /
+        the entropy decoder rejects), for an engine's calibration sample, and, with
+        ``TCA_DEVICE_ENCODINGS=0``, for every raw ``Image`` that is not packed rgb8 (bgr8 /
         rgba8 / bgra8, mono8 / mono16, YUV 4:2:2, 8-bit Bayer, padded rows): HxWx3 uint8 RGB.
         ValueError for an ``Image`` encoding ``ops.golden.image_to_rgb8`` does not know."""
         from ..ros import compat
@@ -266,7 +305,13 @@ class LiveCamera:
                 return ("jpeg", (geo.height, geo.width), geo)
             rgb = self.host_rgb(m)
             return ("frames", rgb.shape[:2], None)
-        return ("frames", (int(m.height), int(m.width)), None)
+        H, W, enc = int(m.height), int(m.width), m.encoding
+        # a raw Image the device converts: any known encoding but packed rgb8 (TCA_DEVICE_ENCODINGS=0:
+        # the host converts them all, as it does the encodings it alone refuses by name)
+        if (enc in golden.IMAGE_ENCODINGS and not (enc == "rgb8" and m.step == 3 * W)
+                and os.environ.get("TCA_DEVICE_ENCODINGS", "1") != "0"):
+            return ("raw", (H, W), (enc, int(m.step), int(bool(m.is_bigendian)) if enc == "mono16" else 0))
+        return ("frames", (H, W), None)
 
     def _engine(self, key, draw: bool, names: Tuple[str, ...], sample_msg) -> _CameraEngine:
         k = (key, draw, names)

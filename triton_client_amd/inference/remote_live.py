@@ -13,7 +13,8 @@ steps to the client's GPU:
 * decode: C++ Huffman decode (``csrc/runtime/jpeg_entropy.cpp``, host threads,
   no GIL) into page-locked staging -> H2D -> HIP IDCT + colour
   (``csrc/kernels/jpeg.hip``) into a device frame batch; raw ``Image`` rows are
-  gathered by C++ threads and uploaded;
+  gathered by C++ threads and uploaded, packed rgb8 as it is and every other
+  encoding as sent, converted to rgb8 on the GPU (``csrc/kernels/encodings.hip``);
 * preprocess: K1 (``tca_image_preprocess``: stretch / letterbox, scaling, layout)
   -> the model input, one D2H into page-locked staging that the C++ wire encoder
   serialises from directly (``channel/wire.py``: no NumPy copy);
@@ -48,8 +49,8 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..ops.image import draw_annotations_, preprocess
-from ..ops.jpeg import GEOM_FIELDS, JpegGeometry
+from ..ops.image import draw_annotations_, image_frame_bytes, image_to_rgb8, preprocess
+from ..ops.jpeg import GEOM_FIELDS
 from ..ros import msgs
 from ..utils.trace import trace_range
 from .live import LiveCamera, _buffers, _is_compressed, _threads, gather_copy
@@ -60,9 +61,13 @@ log = logging.getLogger("triton_client_amd.remote_live")
 class _Ingest:
     """One input kind + frame geometry: messages -> uint8 RGB frames [n, H, W, 3] on the GPU."""
 
-    def __init__(self, kind: str, hw: Tuple[int, int], geo: Optional[JpegGeometry], device, threads: int):
+    def __init__(self, kind: str, hw: Tuple[int, int], geo, device, threads: int):
+        """geo: the :class:`JpegGeometry` of ``"jpeg"``, (encoding, step, is_bigendian) of ``"raw"``."""
         self.kind, self.hw, self.geo, self.device, self.threads = kind, hw, geo, device, threads
-        if geo is not None:
+        if kind == "raw":
+            self.raw_bytes = image_frame_bytes(hw[0], hw[1], geo[1], geo[0])  # ValueError: a geometry it refuses
+            self.raw_stride = (self.raw_bytes + 15) // 16 * 16
+        if kind == "jpeg":
             self.geom_rec = np.array([geo.width, geo.height, geo.nc, geo.hmax, geo.vmax, geo.mcux, geo.mcuy,
                                       *[v for hv in geo.sampling for v in hv], geo.nblocks, 0, 0], np.int32)
 
@@ -93,6 +98,17 @@ class _Ingest:
                     rgb = torch.from_numpy(LiveCamera.host_rgb(datas[i], self.hw)).pin_memory()
                     frames[i].copy_(rgb, non_blocking=True)
             return frames
+        if self.kind == "raw":  # the payloads as sent -> one H2D -> HIP conversion to rgb8
+            enc, step, be = self.geo
+            for m in batch:  # a short payload: the host path's ValueError, before anything is staged
+                if len(m.data) < self.raw_bytes:
+                    LiveCamera.host_rgb(m, self.hw)
+                    raise ValueError(f"{enc!r} image: {len(m.data)} B of data, {self.raw_bytes} B needed")
+            host = torch.empty((n, self.raw_stride), dtype=torch.uint8, pin_memory=True)
+            gather_copy([host.data_ptr() + i * self.raw_stride for i in range(n)], [m.data for m in batch],
+                        [self.raw_bytes] * n, self.threads)
+            return image_to_rgb8(host.to(dev, non_blocking=True), H, W, step, enc, be, out=frames,
+                                 stream=torch.cuda.current_stream(dev))
         host = torch.empty((n, H, W, 3), dtype=torch.uint8, pin_memory=True)
         hn = host.numpy()
         direct, srcs = [], []

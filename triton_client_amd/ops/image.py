@@ -236,6 +236,53 @@ def yolo_stem_fused(frames: torch.Tensor, dst_hw: Tuple[int, int], mode: str, st
     return out, xf
 
 
+def image_frame_bytes(height: int, width: int, step: int, encoding: str) -> int:
+    """Payload bytes ``image_to_rgb8`` reads of one raw ``Image``: every row's pitch but the
+    last row's padding.  The ValueErrors of ``golden.check_image_geometry``."""
+    return (int(height) - 1) * int(step) + golden.check_image_geometry(int(height), int(width), int(step), encoding)
+
+
+def image_to_rgb8(src: torch.Tensor, height: int, width: int, step: int, encoding: str, is_bigendian: int = 0,
+                  out: torch.Tensor | None = None, n: int | None = None, stream=None) -> torch.Tensor:
+    """Raw ``sensor_msgs/Image`` payloads -> rgb8 (``csrc/kernels/encodings.hip``
+    ``tca_image_to_rgb8``; capture-safe), byte for byte ``golden.image_to_rgb8`` of each frame.
+
+    src: uint8 [B, frame_stride], row b the payload of frame b (rows of pitch ``step``; at
+    least ``(H - 1) * step + packed row`` bytes).  The first ``n`` (default B) frames are
+    converted into ``out`` [B, H, W, 3] uint8 (rows packed; allocated if None); the other
+    rows of ``out`` are left as they are.  ValueError, naming the encoding, for an unknown
+    encoding or a geometry ``golden.check_image_geometry`` refuses."""
+    H, W, step = int(height), int(width), int(step)
+    need = image_frame_bytes(H, W, step, encoding)
+    if src.dim() != 2 or src.dtype != torch.uint8 or (src.shape[1] > 1 and src.stride(1) != 1):
+        raise ValueError("src must be uint8 [B, frame_stride] with contiguous rows")
+    B = src.shape[0]
+    n = B if n is None else int(n)
+    if not 0 <= n <= B:
+        raise ValueError(f"{n} frames of a batch of {B}")
+    if src.shape[1] < need:
+        raise ValueError(f"{encoding!r} image {W}x{H} step {step}: {src.shape[1]} B of data")
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=src.device)
+    if (tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.uint8 or out.device != src.device
+            or out.stride(3) != 1 or out.stride(2) != 3 or out.stride(1) != 3 * W):
+        raise ValueError(f"out must be uint8 [{B}, {H}, {W}, 3] with packed rows on {src.device}")
+    sfs, dfs = (src.stride(0), out.stride(0)) if B > 1 else (max(src.shape[1], 1), H * W * 3)
+    if sfs < need or dfs < H * W * 3:
+        raise ValueError(f"{encoding!r} image {W}x{H} step {step}: frames overlap (strides {sfs}, {dfs})")
+    if n * max(sfs, dfs) >= 1 << 31:
+        raise ValueError(f"{encoding!r} batch of {n} x {max(sfs, dfs)} B: 2 GiB or more in one call")
+    be = int(bool(is_bigendian))
+    if src.is_cuda:
+        if n:
+            _native.call("tca_image_to_rgb8", _native.ptr(src), sfs, step, H, W, golden.IMAGE_ENCODINGS[encoding], be,
+                         _native.ptr(out), dfs, n, _native.stream_ptr(stream))
+        return out
+    for b in range(n):
+        out[b] = torch.from_numpy(golden.image_to_rgb8(src[b, :need].numpy(), H, W, step, encoding, be))
+    return out
+
+
 def draw_boxes_(frames: torch.Tensor, box: torch.Tensor, cls: torch.Tensor, count: torch.Tensor,
                 thickness: int = 2, stream=None) -> torch.Tensor:
     """K15: draw result boxes onto uint8 frames in place (``csrc/kernels/draw.hip``).

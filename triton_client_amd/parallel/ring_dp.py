@@ -4,8 +4,10 @@ Rank 0 runs the ROS driver (:class:`~triton_client_amd.inference.ros_inference.R
 / ``RosInference3D``) with one of these in place of the local engine; every
 other rank runs :meth:`serve`.  A node step:
 
-1. rank 0 writes the batch's raw message payloads (JPEG bytes, rgb8 rows,
-   PointCloud2 records) and an item table into the next ring slot
+1. rank 0 writes the batch's raw message payloads (JPEG bytes, rgb8 rows, the
+   rows of any other ``Image`` encoding as the sensor sent them -- each rank's
+   device converts its own shard to rgb8 --, PointCloud2 records) and an item
+   table into the next ring slot
    (:mod:`.host_ring`) and publishes the slot's sequence number;
 2. every participant takes its contiguous shard out of the shared, page-locked
    slot over its own PCIe link and runs the same device path as a single GPU
@@ -54,8 +56,9 @@ from ..ros import msgs
 from .dp import DistInfo, FrameExchange, HealthMonitor
 from .host_ring import MAX_ITEMS, HostRing
 
-KIND_STOP, KIND_JPEG, KIND_FRAMES, KIND_CLOUDS = -1, 1, 2, 3
-# header ints
+KIND_STOP, KIND_JPEG, KIND_FRAMES, KIND_CLOUDS, KIND_RAW = -1, 1, 2, 3, 4
+# header ints (H_KEY..: the step's key; camera: H, W and, for KIND_RAW, the encoding's code in
+# ops.golden.IMAGE_ENCODINGS, step, is_bigendian)
 H_SEQ, H_KIND, H_N, H_GEN, H_SLOT, H_MASK, H_PER, H_DRAW, H_KEY = 0, 1, 2, 3, 4, 5, 6, 7, 8
 H_CALIB = 60  # 1: rank 0 broadcasts its freshly calibrated weights in this step (every rank joins)
 H_FILE = 61  # 1: file-sourced items read from the slot's path (sharded replay)
@@ -513,13 +516,24 @@ class DataParallelDetector2D(_RingDP):
 
     def _prepare(self, m):
         """(key, payload) for the ring: (KIND_JPEG, H, W) with the JPEG bytes when the
-        device path decodes it, else (KIND_FRAMES, H, W) with rgb8 rows."""
+        device path decodes it, (KIND_RAW, H, W, code, step, is_bigendian) with the raw
+        ``Image`` payload as sent when the device path converts it, else (KIND_FRAMES, H, W)
+        with rgb8 rows."""
         from ..inference.live import LiveCamera, _is_compressed
+        from ..ops.golden import IMAGE_ENCODINGS
+        from ..ops.image import image_frame_bytes
 
-        if self.gpu and _is_compressed(m):
+        if self.gpu:
             key = self.local.live()._key(m)
             if key[0] == "jpeg":
                 return (KIND_JPEG, key[1][0], key[1][1]), m.data, m
+            if key[0] == "raw":
+                (H, W), (enc, step, be) = key[1:]
+                need = image_frame_bytes(H, W, step, enc)
+                if len(m.data) < need:
+                    LiveCamera.host_rgb(m)  # the host path's ValueError
+                    raise ValueError(f"{enc!r} image: {len(m.data)} B of data, {need} B needed")
+                return (KIND_RAW, H, W, IMAGE_ENCODINGS[enc], step, be), memoryview(m.data)[:need], m
         if not _is_compressed(m) and m.encoding == "rgb8" and m.step == 3 * m.width:
             return (KIND_FRAMES, int(m.height), int(m.width)), memoryview(m.data)[:m.height * m.step], m
         rgb = LiveCamera.host_rgb(m)
@@ -539,15 +553,15 @@ class DataParallelDetector2D(_RingDP):
         return out
 
     def _step_camera(self, key, payloads, messages, draw):
-        kind, H, W = key
-        frame = H * W * 3
+        kind, H, W = key[:3]
+        frame = H * W * 3  # the annotated rgb8 frame, whatever the input's encoding
         out_sizes = [frame] * len(payloads) if draw else []
         metas = [(0, 0)] * len(payloads)
 
         def prebuild():
             live = self.local.live()
             live._engine(live._key(messages[0]), draw, tuple(self.names), messages[0])
-        return self._run_step(kind, payloads, metas, out_sizes, (H, W), draw,
+        return self._run_step(kind, payloads, metas, out_sizes, key[1:], draw,
                               lambda dst, wk, per, items, view, own, s: self._assemble(
                                   dst, wk, per, items, view, own, s, messages, H, W, draw), prebuild)
 
@@ -559,13 +573,25 @@ class DataParallelDetector2D(_RingDP):
     def _shard_items(self, hdr, items, view, lo, hi):
         return self._shard_messages(hdr, items, view, lo, hi)
 
+    @staticmethod
+    def _raw_key(hdr) -> Tuple[str, int, int]:
+        """(encoding, step, is_bigendian) of a KIND_RAW step."""
+        from ..ops.golden import IMAGE_ENCODINGS
+        name = {c: e for e, c in IMAGE_ENCODINGS.items()}[int(hdr[H_KEY + 2])]
+        return name, int(hdr[H_KEY + 3]), int(hdr[H_KEY + 4])
+
     def _shard_messages(self, hdr, items, view, lo, hi):
         kind, H, W = int(hdr[H_KIND]), int(hdr[H_KEY]), int(hdr[H_KEY + 1])
+        if kind == KIND_RAW:
+            enc, step, be = self._raw_key(hdr)
         out = []
         for i in range(lo, hi):
             raw = self._raw(items, i, view)
             if kind == KIND_JPEG:
                 out.append(msgs.CompressedImage(format="jpeg", data=memoryview(raw)))
+            elif kind == KIND_RAW:  # the payload as rank 0 received it: this rank's device converts it
+                out.append(msgs.Image(height=H, width=W, encoding=enc, step=step, is_bigendian=be,
+                                      data=memoryview(raw)))
             else:
                 out.append(msgs.Image(height=H, width=W, encoding="rgb8", step=3 * W, data=memoryview(raw)))
         return out
@@ -578,8 +604,13 @@ class DataParallelDetector2D(_RingDP):
         batch = self._shard_messages(hdr, items, view, lo, hi)
         if self.gpu:
             live = self.local.live()
-            key = live._key(batch[0]) if batch else (("jpeg" if int(hdr[H_KIND]) == KIND_JPEG else "frames"),
-                                                     (H, W), None)
+            kind = int(hdr[H_KIND])
+            if batch:
+                key = live._key(batch[0])
+            elif kind == KIND_RAW:
+                key = ("raw", (H, W), self._raw_key(hdr))
+            else:
+                key = ("jpeg" if kind == KIND_JPEG else "frames", (H, W), None)
             if not batch and key[0] == "jpeg":
                 raise RingStepError("empty JPEG shard without a geometry")
             eng = live._engine(key, draw, tuple(self.names), self._calibration_sample(hdr, items, view))
