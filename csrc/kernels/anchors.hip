@@ -235,8 +235,14 @@ __global__ void __launch_bounds__(256) anchor_hist_kernel(const T* __restrict__ 
     int d = 0;
     if (aidx < a1) {
       const int a = aidx % A, yx = aidx / A, y = yx / W, x = yx - y * W;
+      // the decode kernel's first-maximum rule, not fmaxf: for classes (-0.0, +0.0) fmaxf gives +0.0
+      // but the decode keeps -0.0, whose key is lower, so the threshold would count anchors the
+      // keyed decode then drops
       float best = -INFINITY;
-      for (int c = 0; c < C; ++c) best = fmaxf(best, head_at(cls, layout, b, H, W, A * C, ld_cls, y, x, a * C + c));
+      for (int c = 0; c < C; ++c) {
+        const float v = head_at(cls, layout, b, H, W, A * C, ld_cls, y, x, a * C + c);
+        if (v > best) best = v;
+      }
       const uint32_t u = float_to_ordered(best);
       if (level == 1) {
         m = true;
