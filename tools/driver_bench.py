@@ -86,6 +86,8 @@ def main():
                     help="publish raw sensor_msgs/Image messages in this encoding (rgb8, bgr8, rgba8, bgra8, mono8, "
                          "mono16, yuv422, yuv422_yuy2, bayer_rggb8, ...) instead of JPEG CompressedImage")
     ap.add_argument("--lidar", type=int, default=512, help="PointCloud2 messages (0: skip)")
+    ap.add_argument("--bev", action="store_true",
+                    help="LiDAR side: also publish the bird's-eye-view Image of every cloud (RosInference3D bev_topic)")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -180,7 +182,8 @@ def main():
                                             is_dense=True))
         st = _Stages()
         drv = RosInference3D(engine=eng3, params={"sub_topic": "/pc", "pub_topic": "/pc_out"}, bus=bus,
-                             batch=a.batch, workers=a.workers, metrics=st, queue_size=window)
+                             batch=a.batch, workers=a.workers, metrics=st, queue_size=window,
+                             bev_topic="/pc_bev" if a.bev else None)
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout)
         st.sum.clear(), st.n.clear()
@@ -191,6 +194,9 @@ def main():
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
                         "input": f"PointCloud2 {clouds[0].width} points x {clouds[0].point_step} B",
                         "output": "jsk BoundingBoxArray (label 2, score > 0.5)", "stages": st.summary()}
+        if a.bev:
+            v = drv.bev_view
+            out["lidar"]["output"] += f" + bev Image {v.W}x{v.H} (host painter)"
     bus.close()
     print(json.dumps(out), flush=True)
     if info is not None:

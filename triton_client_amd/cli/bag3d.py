@@ -5,7 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import DATA, add_framework_flags, add_reference_flags, labels_arg, load_params, setup_logging
+from .common import (DATA, add_framework_flags, add_reference_flags, bev_view, labels_arg, load_params,
+                     setup_logging)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -17,6 +18,9 @@ def parse_args(argv=None):
     p.add_argument("--out-bag", default="", help="output bag (default <bag>_output.bag, 'none' to skip)")
     p.add_argument("--start-seq", type=int, default=0)
     p.add_argument("--max-frames", type=int, default=None)
+    p.add_argument("--bev-out", default="", metavar="DIR",
+                   help="save every cloud's bird's-eye-view picture (points + all detections) as DIR/NNNN.png")
+    p.add_argument("--bev-res", type=float, default=0.1, metavar="M", help="metres per pixel of --bev-out")
     return p.parse_args(argv)
 
 
@@ -39,7 +43,8 @@ def main(argv=None) -> int:
                          out_bag=None if flags.out_bag == "none" else flags.out_bag,
                          batch=max(1, flags.frames_per_step), start_seq=flags.start_seq,
                          max_frames=flags.max_frames, verbose=flags.verbose, jsk=not flags.detection3d,
-                         labels=labels_arg(flags.labels), score_thresh=flags.score_thresh)
+                         labels=labels_arg(flags.labels), score_thresh=flags.score_thresh,
+                         bev_out=flags.bev_out or None, bev_view=bev_view(engine, flags.bev_res, flags.bev_out))
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

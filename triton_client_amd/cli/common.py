@@ -143,6 +143,21 @@ def labels_arg(s: str):
     return None if s in ("all", "", "none") else tuple(int(v) for v in s.split(","))
 
 
+def bev_view(engine, res: float, enabled):
+    """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
+    range for an engine that does not know its model's) at ``res`` metres per pixel; None
+    when the flag that turns the picture on is empty."""
+    if not enabled:
+        return None
+    from ..utils.bev import BevView
+
+    cfg = getattr(engine, "cfg", None)
+    if getattr(cfg, "voxel", None) is not None:
+        return BevView.for_model(cfg, res)
+    d = BevView()
+    return BevView(d.x_range, d.y_range, float(res), d.z_range)
+
+
 def play_bag(path: str, bus, topics=None, rate: Optional[float] = None, shutdown: bool = True):
     """rosbag-play equivalent onto the in-process bus (background thread)."""
     import threading

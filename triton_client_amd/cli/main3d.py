@@ -5,7 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import DATA, add_framework_flags, add_reference_flags, labels_arg, load_params, play_bag, setup_logging
+from .common import (DATA, add_framework_flags, add_reference_flags, bev_view, labels_arg, load_params, play_bag,
+                     setup_logging)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -13,6 +14,9 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__)
     add_reference_flags(p, "pointpillar_kitti")
     add_framework_flags(p, os.path.join(DATA, "client_parameter_3d.yaml"), three_d=True)
+    p.add_argument("--bev-topic", default="", metavar="TOPIC",
+                   help="also publish an rgb8 Image of every cloud from above (points + all detections) here")
+    p.add_argument("--bev-res", type=float, default=0.1, metavar="M", help="metres per pixel of --bev-topic")
     return p.parse_args(argv)
 
 
@@ -37,7 +41,8 @@ def main(argv=None) -> int:
     drv = RosInference3D(channel, client, engine=engine, params=params, bus=bus, jsk=not flags.detection3d,
                          labels=labels_arg(flags.labels), score_thresh=flags.score_thresh,
                          queue_size=None if flags.play else 50,
-                       batch=flags.live_batch, workers=flags.live_workers)
+                         batch=flags.live_batch, workers=flags.live_workers, bev_topic=flags.bev_topic or None,
+                         bev_view=bev_view(engine, flags.bev_res, flags.bev_topic))
     if flags.play:
         play_bag(flags.play, bus, topics=[params["sub_topic"]])
     drv.start_inference(spin=True, timeout=flags.spin_timeout)

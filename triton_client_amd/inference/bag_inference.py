@@ -104,8 +104,15 @@ def _save_png(path, im) -> None:
 
 class BagInference3D(RosInference3D):
     def __init__(self, channel=None, client=None, bagfile: str = "", out_bag: Optional[str] = "", batch: int = 8,
-                 start_seq: int = 0, max_frames: Optional[int] = None, verbose: bool = False, **kw):
+                 start_seq: int = 0, max_frames: Optional[int] = None, verbose: bool = False,
+                 bev_out: Optional[str] = None, **kw):
+        """bev_out: a directory; every cloud's bird's-eye-view picture is saved there as
+        ``NNNN.png`` (the naming of the 2D replay's ``out_dir``) and, with an output bag,
+        written to it on ``bev_topic`` (default ``<pub_topic>/bev``)."""
         super().__init__(channel, client, **kw)
+        self.bev_out = bev_out or None
+        if self.bev_out and not self.bev_topic:
+            self.enable_bev(self.params["pub_topic"] + "/bev", kw.get("bev_view"))
         self.bagfile, self.batch, self.start_seq, self.max_frames = bagfile, batch, start_seq, max_frames
         self.out_bag = (os.path.splitext(bagfile)[0] + "_output.bag") if out_bag == "" else out_bag
         self.verbose = verbose
@@ -114,6 +121,8 @@ class BagInference3D(RosInference3D):
 
     def start_inference(self, spin: bool = False, timeout: Optional[float] = None):
         p = self.params
+        if self.bev_out:
+            os.makedirs(self.bev_out, exist_ok=True)
         ob = Bag(self.out_bag, "w") if self.out_bag else None
         count = 0
         t0 = time.perf_counter()
@@ -125,10 +134,14 @@ class BagInference3D(RosInference3D):
                     chunk = chunk[: max(0, self.max_frames - count)]
                     if not chunk:
                         break
-                for m, (out, pred) in zip(chunk, self.process(chunk)):
+                for m, (out, pred, *pic) in zip(chunk, self.process(chunk)):
+                    if pic and self.bev_out:
+                        _save_png(os.path.join(self.bev_out, f"{count:04}.png"), pic[0])
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
                         ob.write(p["pub_topic"], out)
+                        if pic:
+                            ob.write(self.bev_topic, pic[0])
                     if self.verbose:
                         print(m.header.seq)
                     self.results.append((m.header.seq, pred))

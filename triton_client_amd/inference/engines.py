@@ -93,10 +93,26 @@ class Detector2D(ABC):
 
 class Detector3D(ABC):
     names: List[str] = []
+    label_base: int = 1  # the pred_labels value of names[0] (OpenPCDet labels start at 1)
 
     @abstractmethod
     def detect(self, clouds: Sequence[msgs.PointCloud2]) -> List[dict]:
         """PointCloud2 messages → per-cloud {pred_boxes, pred_scores, pred_labels}."""
+
+    def render_bev(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict], view) -> List[np.ndarray]:
+        """The bird's-eye-view picture of each cloud and its predictions with the host painter
+        (``utils.bev.render_bev_frame``), from the points as this engine preprocesses them."""
+        from ..ros.compat import cloud_to_numpy
+        from ..utils.bev import label_names, render_bev_frame
+
+        zo = float(getattr(self, "z_offset", 0.0))
+        names = label_names(getattr(self, "names", None) or [], getattr(self, "label_base", 1))
+        out = []
+        for c, p in zip(clouds, preds):
+            pts = cloud_to_numpy(c, normalize_intensity=getattr(self, "normalize", True), z_offset=zo)
+            out.append(render_bev_frame(pts, None, p["pred_boxes"], p["pred_scores"], p["pred_labels"], None, view,
+                                        names, zo))
+        return out
 
 
 def pack_task_segments(res, k: int, max_out: int):
@@ -356,6 +372,7 @@ class LocalDetector3D(Detector3D):
             self.cfg = cfg or CenterPointConfig()
             self.model = build_centerpoint(self.cfg, seed)
         self.box_dim = 9 if family == "centerpoint" else 7
+        self.label_base = 0 if family == "centerpoint" else 1
         self.B, self.normalize = batch, normalize_intensity
         self.z_offset = self.Z_OFFSET[family] if z_offset is None else z_offset
         self.graph = graph and self.device.type == "cuda"

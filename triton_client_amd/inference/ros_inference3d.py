@@ -7,6 +7,12 @@ z offset +1.5 before voxelising (removed from the output boxes), intensity
 normalised by its max, only label 2 (Pedestrian) with score > 0.5 published,
 jsk dimensions swapped (x = dy, y = dx).  Fixed: the Detection3DArray yaw is
 taken from the box's own dimension (index 6 for 7-d boxes, 8 for 9-d; A8).
+
+``bev_topic``: also publish, per cloud and with the cloud's header, an rgb8
+``Image`` of the frame from above — points grey by height, every detection the
+engine returned (whatever ``labels`` / ``score_thresh`` keep in the box
+message) as a labelled box, rendered by the host painter ``utils/bev.py``
+for every engine.
 """
 from __future__ import annotations
 
@@ -81,10 +87,14 @@ class RosInference3D(BaseInference):
     def __init__(self, channel=None, client=None, engine: Optional[Detector3D] = None, params: Optional[dict] = None,
                  bus=None, jsk: bool = True, labels: Optional[Sequence[int]] = (2,), score_thresh: float = 0.5,
                  z_offset: float = 1.5, queue_size: Optional[int] = 50, metrics=None, mode: str = "sync",
-                 wire: str = "raw", batch: int = 1, workers: int = 1):
+                 wire: str = "raw", batch: int = 1, workers: int = 1, bev_topic: Optional[str] = None,
+                 bev_view=None):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
+        self.bev_topic, self.bev_view, self.bev_pub = None, None, None
+        if bev_topic:
+            self.enable_bev(bev_topic, bev_view)
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
@@ -99,10 +109,13 @@ class RosInference3D(BaseInference):
         p = self.params
         t = msgs.BoundingBoxArray if self.jsk else msgs.Detection3DArray
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
+        if self.bev_topic:
+            self.bev_pub = compat.Publisher(self.bev_topic, msgs.Image, queue_size=1, bus=self.bus)
         cb, qs = self._pc_callback, self.queue_size
         if self.batch > 1 or self.workers > 1:
             from .batching import MicroBatchRunner
-            self.runner = MicroBatchRunner(lambda cs: [m for m, _ in self.process(cs)], self.pub.publish,
+            self.runner = MicroBatchRunner(lambda cs: [(r[0], r[2] if len(r) > 2 else None) for r in self.process(cs)],
+                                           self._publish,
                                            batch=self.batch, workers=self.workers,
                                            capacity=max(self.queue_size or 0, 2 * self.batch * self.workers))
             cb, qs = self.runner.push, None
@@ -119,6 +132,21 @@ class RosInference3D(BaseInference):
             self.runner.close(drain=drain)
             self.runner = None
 
+    def enable_bev(self, topic: str, view=None) -> None:
+        """Publish the bird's-eye-view picture on ``topic``; ``view``: a ``BevView`` (default:
+        the engine's point-cloud range at 0.1 m per pixel, else the KITTI range)."""
+        from ..utils.bev import BevView
+
+        cfg = getattr(self.engine, "cfg", None)
+        self.bev_topic = topic
+        self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
+
+    def _publish(self, item) -> None:
+        m, im = item
+        self.pub.publish(m)
+        if im is not None and self.bev_pub is not None:
+            self.bev_pub.publish(im)
+
     def to_msg(self, pred: dict, header: msgs.Header):
         idx = select_boxes(pred, self.labels, self.score_thresh)
         hdr = msgs.Header(seq=header.seq, stamp=header.stamp, frame_id=header.frame_id)
@@ -132,13 +160,26 @@ class RosInference3D(BaseInference):
         return self._live_exec
 
     def process(self, clouds: Sequence[msgs.PointCloud2]) -> List[tuple]:
+        """-> [(box message, prediction)] per cloud; with ``bev_topic``,
+        [(box message, prediction, bird's-eye-view Image)]."""
         t0 = time.perf_counter()
         timer = StageTimer(self.metrics)
         live = self._live()
+        view, pics = self.bev_view, None
         with timer("detect3d"):
             preds = live.process(clouds) if live is not None else self.engine.detect(clouds)
+        if view is not None:
+            with timer("bev_render"):
+                fn = getattr(self.engine, "render_bev", None)  # (an engine that is no Detector3D subclass)
+                pics = fn(clouds, preds, view) if fn is not None else Detector3D.render_bev(self.engine, clouds,
+                                                                                            preds, view)
         with timer("boxes_publish"):
             out = [(self.to_msg(p, c.header), p) for c, p in zip(clouds, preds)]
+            if pics is not None:
+                out = [(m, p, msgs.Image(header=c.header, height=view.H, width=view.W, encoding="rgb8",
+                                         is_bigendian=0, step=3 * view.W,
+                                         data=memoryview(np.ascontiguousarray(f).reshape(-1))))
+                       for (m, p), c, f in zip(out, clouds, pics)]
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -146,5 +187,5 @@ class RosInference3D(BaseInference):
         return out
 
     def _pc_callback(self, msg):
-        for m, _ in self.process([msg]):
-            self.pub.publish(m)
+        for r in self.process([msg]):
+            self._publish((r[0], r[2] if len(r) > 2 else None))
