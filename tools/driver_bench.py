@@ -56,7 +56,8 @@ class _Stages:
         return {k: {"calls": self.n[k], "ms_per_call": round(1e3 * v / self.n[k], 3)} for k, v in self.sum.items()}
 
 
-def _run(bus, pub_topic, out_topic, out_type, messages, window, timeout):
+def _run(bus, pub_topic, out_topic, out_type, messages, window, timeout, published=None):
+    """published: a list that receives the payload bytes of every output message."""
     from triton_client_amd.ros import compat
 
     got = []
@@ -64,6 +65,8 @@ def _run(bus, pub_topic, out_topic, out_type, messages, window, timeout):
 
     def on_out(m):
         got.append(time.perf_counter())
+        if published is not None:
+            published.append(len(m.data))
         if len(got) >= len(messages):
             done.set()
     sub = compat.Subscriber(out_topic, out_type, on_out, bus=bus)
@@ -85,6 +88,11 @@ def main():
     ap.add_argument("--camera-encoding", default=None, metavar="NAME",
                     help="publish raw sensor_msgs/Image messages in this encoding (rgb8, bgr8, rgba8, bgra8, mono8, "
                          "mono16, yuv422, yuv422_yuy2, bayer_rggb8, ...) instead of JPEG CompressedImage")
+    ap.add_argument("--compressed-out", action="store_true",
+                    help="camera side: publish the annotated frame as a JPEG CompressedImage on <pub_topic>/compressed "
+                         "(RosInference compressed=; encoded on the GPU) instead of the raw Image")
+    ap.add_argument("--jpeg-quality", type=int, default=90)
+    ap.add_argument("--jpeg-subsampling", default="4:2:0", choices=["4:2:0", "4:2:2", "4:4:4"])
     ap.add_argument("--lidar", type=int, default=512, help="PointCloud2 messages (0: skip)")
     ap.add_argument("--bev", action="store_true",
                     help="LiDAR side: also publish the bird's-eye-view Image of every cloud (RosInference3D bev_topic)")
@@ -156,18 +164,26 @@ def main():
         warm = 2 * a.batch
         msgs_in = _camera_messages(H, W, warm + a.camera, a.camera_encoding)
         st = _Stages()
+        opts = None
+        if a.compressed_out:
+            from triton_client_amd.ops.jpeg_encode import JpegOptions
+            opts = JpegOptions(quality=a.jpeg_quality, subsampling=a.jpeg_subsampling)
         drv = RosInference(engine=eng2, params={"sub_topic": "/cam", "pub_topic": "/cam_out"}, bus=bus,
-                           batch=a.batch, workers=a.workers, metrics=st, queue_size=window)
+                           batch=a.batch, workers=a.workers, metrics=st, queue_size=window, compressed=opts)
         drv.start_inference(spin=False)
-        _run(bus, "/cam", "/cam_out", msgs.Image, msgs_in[:warm], window, a.timeout)  # warm-up + graphs
+        out_type = msgs.CompressedImage if opts is not None else msgs.Image
+        _run(bus, "/cam", drv.out_topic, out_type, msgs_in[:warm], window, a.timeout)  # warm-up + graphs
         st.sum.clear(), st.n.clear()
-        n, dt, ok = _run(bus, "/cam", "/cam_out", msgs.Image, msgs_in[warm:], window, a.timeout)
+        sizes = []
+        n, dt, ok = _run(bus, "/cam", drv.out_topic, out_type, msgs_in[warm:], window, a.timeout, published=sizes)
         drv.stop()
         if info is not None:
             eng2.close()
         out["camera"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
                          "input": _camera_input(H, W, a.camera_encoding),
-                         "output": "annotated Image + Detection2DArray", "stages": st.summary()}
+                         "output": (f"annotated CompressedImage JPEG q{a.jpeg_quality} {a.jpeg_subsampling}"
+                                    if opts is not None else "annotated Image") + " + Detection2DArray",
+                         "published_bytes_per_frame": round(sum(sizes) / max(1, len(sizes))), "stages": st.summary()}
     if a.lidar:
         spec = LidarSpec(sensor_height=3.23)
         clouds = [compat.create_cloud_xyzi(np.frombuffer(lidar_sweep(spec, s).tobytes(), np.float32).reshape(-1, 4))

@@ -32,6 +32,15 @@ _KERNEL_SIGS = {
     # JPEG pixel reconstruction (csrc/kernels/jpeg.hip)
     "tca_jpeg_idct": [P, P, P, P, L, L, I, P],
     "tca_jpeg_color": [P, P, P, L, L, I, P],
+    # JPEG encoding (csrc/kernels/jpeg_encode.hip)
+    # frames, qt, coef, geom, frame stride, coef stride (blocks), n, stream
+    "tca_jpeg_fdct": [P, P, P, P, L, L, I, P],
+    # coef, tabs, geom, coef stride (blocks), restart, seg_size, nseg, n, stream
+    "tca_jpeg_enc_size": [P, P, P, L, I, P, I, I, P],
+    # seg_size, seg_off, nseg, hdr, hlen, out, cap, lens, n, stream
+    "tca_jpeg_enc_scan": [P, P, I, P, I, P, L, P, I, P],
+    # coef, tabs, geom, coef stride (blocks), restart, seg_off, nseg, hlen, out, cap, lens, n, stream
+    "tca_jpeg_enc_write": [P, P, P, L, I, P, I, I, P, L, P, I, P],
     # src, src frame stride, step, H, W, code, is_bigendian, dst, dst frame stride, n, stream
     # (csrc/kernels/encodings.hip)
     "tca_image_to_rgb8": [P, L, I, I, I, I, I, P, L, I, P],

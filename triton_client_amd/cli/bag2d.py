@@ -5,7 +5,7 @@ import argparse
 import os
 import sys
 
-from .common import DATA, add_framework_flags, add_reference_flags, load_params, setup_logging
+from .common import DATA, add_framework_flags, add_reference_flags, jpeg_options, load_params, setup_logging
 from .engines import engine_2d, export_if_asked, maybe_data_parallel
 
 
@@ -31,6 +31,9 @@ def main(argv=None) -> int:
     info = None
     if flags.engine == "local":
         engine, info = maybe_data_parallel(engine)
+        if info is not None and flags.publish_compressed:  # every rank stops here, before any serves
+            raise SystemExit("--publish-compressed is not available with data-parallel ranks (raw frames travel "
+                             "between them); run one process per GPU")
         if info is not None and not info.is_main:  # worker rank: serve shards until rank 0 is done
             engine.serve()
             from ..parallel.dp import shutdown
@@ -38,7 +41,7 @@ def main(argv=None) -> int:
             return 0
     drv = BagInference2D(channel, client, engine=engine, params=params, bagfile=flags.bag, out_dir=flags.out or None,
                          out_bag=flags.out_bag, batch=max(1, flags.frames_per_step), save_png=bool(flags.out),
-                         start_seq=flags.start_seq, max_frames=flags.max_frames)
+                         start_seq=flags.start_seq, max_frames=flags.max_frames, compressed=jpeg_options(flags))
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

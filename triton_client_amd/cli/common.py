@@ -81,6 +81,12 @@ def add_framework_flags(p: argparse.ArgumentParser, params_default: str, three_d
         g.add_argument("--letterbox", action="store_true", help="letterbox instead of the reference's stretch")
         g.add_argument("--conf-thres", type=float, default=0.3, help="reference: 0.3")
         g.add_argument("--images", default=None, help="directory of images for -i local")
+        g.add_argument("--publish-compressed", action="store_true", default=False,
+                       help="publish the annotated frame as a JPEG CompressedImage on <pub_topic>/compressed instead of "
+                            "the raw Image (local GPU engine: encoded on the device; not with data-parallel ranks)")
+        g.add_argument("--jpeg-quality", type=int, default=90, help="--publish-compressed: JPEG quality 1..100")
+        g.add_argument("--jpeg-subsampling", choices=["4:2:0", "4:2:2", "4:4:4"], default="4:2:0",
+                       help="--publish-compressed: chroma subsampling")
 
 
 def load_params(path: Optional[str], server: Optional[str] = None) -> dict:
@@ -137,6 +143,15 @@ def make_client(flags, channel=None):
 
 def rpc_mode(flags) -> str:
     return "stream" if flags.streaming else "async" if flags.async_set else "sync"
+
+
+def jpeg_options(flags):
+    """The drivers' ``compressed=`` option of --publish-compressed / --jpeg-*; None when off."""
+    if not getattr(flags, "publish_compressed", False):
+        return None
+    from ..ops.jpeg_encode import JpegOptions
+
+    return JpegOptions(quality=flags.jpeg_quality, subsampling=flags.jpeg_subsampling)
 
 
 def labels_arg(s: str):

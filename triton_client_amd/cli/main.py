@@ -5,8 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_framework_flags, add_reference_flags, image_files, load_params, play_bag,
-                     setup_logging)
+from .common import (DATA, add_framework_flags, add_reference_flags, image_files, jpeg_options, load_params,
+                     play_bag, setup_logging)
 from .engines import engine_2d, export_if_asked, maybe_data_parallel
 
 
@@ -29,6 +29,9 @@ def main(argv=None) -> int:
     info = None
     if flags.engine == "local":  # under torchrun: shard every micro-batch over the node's GPUs
         engine, info = maybe_data_parallel(engine)
+        if info is not None and flags.publish_compressed:  # every rank stops here, before any serves
+            raise SystemExit("--publish-compressed is not available with data-parallel ranks (raw frames travel "
+                             "between them); run one process per GPU")
         if info is not None and not info.is_main:
             engine.serve()
             from ..parallel.dp import shutdown
@@ -41,7 +44,7 @@ def main(argv=None) -> int:
     bus = default_bus() if (flags.play or flags.image_src == "local" or not compat.HAVE_ROSPY) else None
     drv = RosInference(channel, client, engine=engine, params=params, bus=bus, metrics=metrics,
                        queue_size=None if flags.play or flags.image_src == "local" else 1,
-                       batch=flags.live_batch, workers=flags.live_workers)
+                       batch=flags.live_batch, workers=flags.live_workers, compressed=jpeg_options(flags))
     if flags.image_src == "local":
         rc = _run_local_images(drv, flags, params)
         export_if_asked(flags, engine)
@@ -78,6 +81,7 @@ def _run_local_images(drv, flags, params) -> int:
     out_dir = os.path.join(flags.images, "detections")
     os.makedirs(out_dir, exist_ok=True)
     step = max(1, flags.frames_per_step)
+    from ..inference.ros_inference import decode_image_msg
     from ..ros import compat
     for s in range(0, len(files), step):
         batch = []
@@ -85,7 +89,7 @@ def _run_local_images(drv, flags, params) -> int:
             img = np.asarray(Image.open(f).convert("RGB"))
             batch.append(compat.numpy_to_imgmsg(img, header=msgs.Header(seq=s + k, frame_id=os.path.basename(f))))
         for m, (im, _, d) in zip(batch, drv.process(batch)):
-            Image.fromarray(compat.imgmsg_to_numpy(im)).save(os.path.join(out_dir, m.header.frame_id + ".png"))
+            Image.fromarray(decode_image_msg(im)).save(os.path.join(out_dir, m.header.frame_id + ".png"))
             print(f"{m.header.frame_id}: {len(d)} detections")
     return 0
 

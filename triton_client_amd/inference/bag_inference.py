@@ -6,7 +6,8 @@ live drivers, but ``batch`` frames at a time (one local graph replay or a
 window of remote RPCs per micro-batch) instead of one blocking RPC per frame.
 2D: annotated PNGs to ``out_dir/NNNN.png`` and, if ``out_bag`` is given, the
 input image + annotated image + Detection2DArray written to it (the
-reference opened ``output.bag`` but never wrote).  3D: the input cloud and
+reference opened ``output.bag`` but never wrote); with ``compressed=`` the annotated
+image is a JPEG ``CompressedImage`` on ``<pub_topic>/compressed``.  3D: the input cloud and
 the BoundingBoxArray are written to ``<bag>_output.bag`` like the
 reference.  Bag path and output dir are arguments (fixes A14);
 ``start_seq`` resumes a replay.
@@ -84,7 +85,7 @@ class BagInference2D(RosInference):
                         _save_png(os.path.join(self.out_dir, f"{count:04}.png"), im)
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
-                        ob.write(p["pub_topic"], im)
+                        ob.write(self.out_topic, im)  # <pub_topic>, or <pub_topic>/compressed (JPEG)
                         ob.write(p["pub_topic"] + "/detections", det)
                     self.results.append((m.header.seq, d))
                     count += 1
@@ -97,9 +98,9 @@ class BagInference2D(RosInference):
 def _save_png(path, im) -> None:
     from PIL import Image as PILImage
 
-    from ..ros.compat import imgmsg_to_numpy
+    from .ros_inference import decode_image_msg
 
-    PILImage.fromarray(imgmsg_to_numpy(im, "rgb8")).save(path)
+    PILImage.fromarray(decode_image_msg(im)).save(path)
 
 
 class BagInference3D(RosInference3D):

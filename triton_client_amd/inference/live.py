@@ -21,7 +21,10 @@ camera (:class:`LiveCamera`)
     captured YOLOv5 / YOLOv4 / Detectron step, and boxes + labels drawn on the resident frames
     (``csrc/kernels/draw.hip``); the annotated frames and the detections come
     back in one D2H into pinned memory that the published ``Image`` wraps
-    without a copy.
+    without a copy.  With ``process(..., compressed=JpegOptions(...))`` the step
+    also encodes the annotated frames (``csrc/kernels/jpeg_encode.hip``) and
+    the files come back instead of the frames, a quarter of the bytes, each
+    wrapped by a ``CompressedImage``.
 LiDAR (:class:`LiveLidar`)
     ``PointCloud2`` payload bytes gathered into a pinned slot -> H2D -> the
     captured unpack / voxelise / network / NMS step -> one D2H of the result
@@ -88,11 +91,13 @@ class _CameraEngine:
     graphs and a pool of pinned staging slots."""
 
     def __init__(self, live: "LiveCamera", kind: str, hw: Tuple[int, int], geo, draw: bool, names: Tuple[str, ...],
-                 sample: np.ndarray):
+                 sample: np.ndarray, compressed=None):
         """geo: the :class:`JpegGeometry` of a ``"jpeg"`` engine, (encoding, step, is_bigendian)
-        of a ``"raw"`` one, else None."""
+        of a ``"raw"`` one, else None.  compressed: :class:`~triton_client_amd.ops.jpeg_encode.JpegOptions`
+        -- the step also encodes the annotated frames, and they leave as ``CompressedImage``."""
         det = live.det
         self.live, self.kind, self.hw, self.draw = live, kind, hw, draw
+        self.compressed, self.names, self.jenc, self.warned = compressed, names, None, False
         raw = geo if kind == "raw" else None
         self.geo = geo = geo if kind == "jpeg" else None
         self.B, dev = det.B, det.device
@@ -106,7 +111,14 @@ class _CameraEngine:
         if draw and names:
             from ..utils.draw import names_table
             self.names_dev = torch.from_numpy(names_table(names)).to(dev)
-        self.ex = StreamExecutor(self._step, [(self.p, "frames")], dev, graph=det.graph)
+        inputs = [(self.p, "frames")]
+        if compressed is not None:  # the files and their lengths are per set, like the frames they replace
+            from ..ops.jpeg_encode import JpegBatchEncoder
+            self.jenc = JpegBatchEncoder(self.B, hw, dev, compressed.quality, compressed.subsampling,
+                                         compressed.restart, compressed.cap)
+            self.jfiles, self.jlens = self.jenc.buffers()
+            inputs += [(self, "jfiles"), (self, "jlens")]
+        self.ex = StreamExecutor(self._step, inputs, dev, graph=det.graph)
         if raw is not None:
             self.raw_dev = [torch.empty((self.B, self.raw_stride), dtype=torch.uint8, device=dev)
                             for _ in range(self.ex.sets)]
@@ -138,6 +150,9 @@ class _CameraEngine:
             from ..ops.image import draw_annotations_
             draw_annotations_(self.p.frames, res.box, res.score, res.cls, res.count, self.names_dev,
                               thickness=self.live.thickness)
+        if self.jenc is not None:
+            # all B frames, whatever the batch holds: the captured step's grids are fixed
+            self.jenc.encode_(self.p.frames, self.jfiles, self.jlens, stream=torch.cuda.current_stream())
         return res
 
     # ------------------------------------------------------------------ host staging
@@ -222,7 +237,11 @@ class _CameraEngine:
                 def copies(k):
                     return [(self.ex.inputs[k][0], s.frames[:n])]
                 pre = None
-            if out_frames is not None:
+            if self.jenc is not None:
+                if out_frames is not None:
+                    raise ValueError("compressed output has no caller-provided frame buffers")
+                ticket = self.ex.submit(copies, pre, lambda k: [self.ex.inputs[k][1][:n], self.ex.inputs[k][2][:n]])
+            elif out_frames is not None:
                 ticket = self.ex.submit(copies, pre, lambda k: [self.ex.inputs[k][0][i] for i in range(n)],
                                         extras_dst=list(out_frames))
             else:
@@ -234,13 +253,17 @@ class _CameraEngine:
         return SimpleNamespace(batch=batch, ticket=ticket, out_frames=out_frames)
 
     def finish(self, pend) -> List[tuple]:
-        """-> [(Image, dets [n, 6])] of a submitted batch (waits for its D2H)."""
+        """-> [(Image, dets [n, 6])] of a submitted batch (waits for its D2H); with
+        compressed output the first of each pair is a ``CompressedImage``."""
         ticket, batch = pend.ticket.wait(), pend.batch
         res = ticket.result()
         cnt = res.count.numpy()
         box, score, cls = res.box.numpy(), res.score.numpy(), res.cls.numpy()
         H, W = self.hw
-        frames = [f.numpy() for f in ticket.extras] if pend.out_frames is not None else ticket.extras[0].numpy()
+        if self.jenc is not None:
+            files, lens = ticket.extras[0].numpy(), ticket.extras[1].numpy()
+        else:
+            frames = [f.numpy() for f in ticket.extras] if pend.out_frames is not None else ticket.extras[0].numpy()
         out = []
         for j, m in enumerate(batch):
             c = int(min(cnt[j], box.shape[1]))
@@ -248,10 +271,31 @@ class _CameraEngine:
             d[:, :4] = box[j, :c, :4]
             d[:, 4] = score[j, :c]
             d[:, 5] = cls[j, :c]
+            if self.jenc is not None:
+                from ..ops.jpeg_encode import FORMAT
+                if lens[j] > 0:  # zero-copy view of the pinned D2H buffer
+                    data = memoryview(files[j, :int(lens[j])])
+                else:
+                    data = self._host_file(m, d, int(-lens[j]))
+                out.append((msgs.CompressedImage(header=m.header, format=FORMAT, data=data), d))
+                continue
             im = msgs.Image(header=m.header, height=H, width=W, encoding="rgb8", is_bigendian=0, step=3 * W,
                             data=memoryview(frames[j].reshape(-1)))  # zero-copy view of the pinned D2H buffer
             out.append((im, d))
         return out
+
+    def _host_file(self, m, dets: np.ndarray, needed: int) -> bytes:
+        """A frame whose file did not fit the device buffer: decoded, drawn and encoded on the host."""
+        from ..ops.jpeg_encode import encode_pil
+        from ..utils.draw import draw_detections
+        if not self.warned:
+            self.warned = True
+            log.warning("a %dx%d frame needs %d B as JPEG, the device buffer holds %d B per frame: such frames "
+                        "are encoded on the host (raise the cap)", self.hw[1], self.hw[0], needed, self.jenc.cap)
+        rgb = np.array(self.live.host_rgb(m, self.hw))
+        if self.draw:
+            draw_detections(rgb, dets, list(self.names) or None, thickness=self.live.thickness)
+        return encode_pil(rgb, self.compressed.quality, self.compressed.subsampling)
 
     def run(self, batch: Sequence) -> List[tuple]:
         return self.finish(self.submit(batch))
@@ -313,8 +357,10 @@ class LiveCamera:
             return ("raw", (H, W), (enc, int(m.step), int(bool(m.is_bigendian)) if enc == "mono16" else 0))
         return ("frames", (H, W), None)
 
-    def _engine(self, key, draw: bool, names: Tuple[str, ...], sample_msg) -> _CameraEngine:
-        k = (key, draw, names)
+    compressed_out = True  # process() takes compressed= (the drivers ask before passing it)
+
+    def _engine(self, key, draw: bool, names: Tuple[str, ...], sample_msg, compressed=None) -> _CameraEngine:
+        k = (key, draw, names) if compressed is None else (key, draw, names, compressed)
         eng = self.engines.get(k)
         if eng is None:
             with self.lock:
@@ -322,11 +368,14 @@ class LiveCamera:
                 if eng is None:
                     kind, hw, geo = key
                     sample = self.host_rgb(sample_msg, hw) if self.det.calibrate_target is not None else None
-                    eng = self.engines[k] = _CameraEngine(self, kind, hw, geo, draw, names, sample)
+                    eng = self.engines[k] = _CameraEngine(self, kind, hw, geo, draw, names, sample, compressed)
         return eng
 
-    def process(self, messages: Sequence, draw: bool = True, names: Optional[Sequence[str]] = None) -> List[tuple]:
-        """-> [(Image, dets [n, 6] x1,y1,x2,y2,conf,cls in frame pixels)] in message order."""
+    def process(self, messages: Sequence, draw: bool = True, names: Optional[Sequence[str]] = None,
+                compressed=None) -> List[tuple]:
+        """-> [(Image, dets [n, 6] x1,y1,x2,y2,conf,cls in frame pixels)] in message order.
+        compressed: :class:`~triton_client_amd.ops.jpeg_encode.JpegOptions`; the annotated frames are
+        encoded on the device and come back as ``CompressedImage`` (JPEG) instead."""
         names = tuple(names or ())
         groups: Dict[tuple, List[int]] = {}
         for i, m in enumerate(messages):
@@ -334,7 +383,7 @@ class LiveCamera:
         out: List[Optional[tuple]] = [None] * len(messages)
         B = self.det.B
         for key, idx in groups.items():
-            eng = self._engine(key, draw, names, messages[idx[0]])
+            eng = self._engine(key, draw, names, messages[idx[0]], compressed)
             for s in range(0, len(idx), B):
                 chunk = idx[s:s + B]
                 for i, r in zip(chunk, eng.run([messages[i] for i in chunk])):

@@ -11,6 +11,12 @@ An empty detection set still publishes the frame (fixes A5).
 run as micro-batches (one engine call — one graph replay, or one DP scatter
 over the node's GPUs — per batch) from a latest-wins window, and results are
 re-published in ``header.seq`` order (:mod:`.batching`).
+
+``compressed=JpegOptions(...)``: the annotated frame is published as a
+``CompressedImage`` (JPEG) on ``<pub_topic>/compressed`` *instead of* the raw
+``Image`` -- about a thirteenth of the bytes.  The local GPU engine encodes on the
+device inside its captured step (``ops/jpeg_encode.py``); every other engine encodes
+the annotated array with PIL on the host.  The data-parallel ring engines refuse it.
 """
 from __future__ import annotations
 
@@ -57,8 +63,12 @@ class RosInference(BaseInference):
     def __init__(self, channel=None, client=None, engine: Optional[Detector2D] = None, params: Optional[dict] = None,
                  bus=None, letterbox: bool = False, conf_thres: float = 0.3, draw: bool = True,
                  publish_detections: bool = True, queue_size: Optional[int] = 1, metrics=None, mode: str = "sync",
-                 wire: str = "raw", batch: int = 1, workers: int = 1):
+                 wire: str = "raw", batch: int = 1, workers: int = 1, compressed=None):
         super().__init__(channel, client)
+        if compressed is not None and not getattr(engine, "compressed_out", True):
+            raise ValueError(f"{type(engine).__name__} does not publish compressed frames: the data-parallel ring "
+                             "engines move raw frames between ranks; run without --publish-compressed")
+        self.compressed = compressed
         self._params = params or {}
         self.engine = engine or RemoteDetector2D(channel, client, letterbox=letterbox, conf_thres=conf_thres,
                                                  mode=mode, wire=wire)
@@ -73,7 +83,11 @@ class RosInference(BaseInference):
     # ------------------------------------------------------------------ run
     def start_inference(self, spin: bool = True, timeout: Optional[float] = None):
         p = self.params
-        self.pub = compat.Publisher(p["pub_topic"], msgs.Image, queue_size=10, bus=self.bus)
+        if self.compressed is not None:  # instead of the raw Image, not beside it
+            self.pub = compat.Publisher(p["pub_topic"] + "/compressed", msgs.CompressedImage, queue_size=10,
+                                        bus=self.bus)
+        else:
+            self.pub = compat.Publisher(p["pub_topic"], msgs.Image, queue_size=10, bus=self.bus)
         if self.publish_detections:
             self.det_pub = compat.Publisher(p["pub_topic"] + "/detections", msgs.Detection2DArray, queue_size=10,
                                             bus=self.bus)
@@ -111,14 +125,32 @@ class RosInference(BaseInference):
             self._live_exec = fn() if callable(fn) else None
         return self._live_exec
 
+    @property
+    def out_topic(self) -> str:
+        """Where the annotated frame goes."""
+        return self.params["pub_topic"] + ("/compressed" if self.compressed is not None else "")
+
+    def _compress(self, im) -> msgs.CompressedImage:
+        """An annotated rgb8 ``Image`` -> JPEG ``CompressedImage`` on the host (PIL)."""
+        from ..ops.jpeg_encode import FORMAT, encode_pil
+        c = self.compressed
+        return msgs.CompressedImage(header=im.header, format=FORMAT,
+                                    data=encode_pil(compat.imgmsg_to_numpy(im, "rgb8"), c.quality, c.subsampling))
+
     def process(self, images: Sequence) -> List[tuple]:
-        """Messages → [(annotated Image msg, Detection2DArray, dets [n,6])]."""
+        """Messages → [(annotated Image msg, Detection2DArray, dets [n,6])]; with ``compressed`` the
+        first of each triple is a JPEG ``CompressedImage``."""
         t0 = time.perf_counter()
         timer = StageTimer(self.metrics)
         live = self._live()
         if live is not None:  # device path: GPU decode, graph step, GPU annotation, zero-copy Image
             with timer("device"):
-                res = live.process(images, draw=self.draw, names=self.class_names)
+                if self.compressed is not None and getattr(live, "compressed_out", False):
+                    res = live.process(images, draw=self.draw, names=self.class_names, compressed=self.compressed)
+                else:
+                    res = live.process(images, draw=self.draw, names=self.class_names)
+                    if self.compressed is not None:  # a device path without the encoder (the remote client's)
+                        res = [(self._compress(im), d) for im, d in res]
             with timer("messages"):
                 out = [(im, detections_to_msg(d, m.header), d) for m, (im, d) in zip(images, res)]
             self.frames += len(images)
@@ -143,6 +175,8 @@ class RosInference(BaseInference):
                 elif self.draw:
                     img = draw_detections(img.copy(), d, self.class_names)
                 im = compat.numpy_to_imgmsg(img, "rgb8", header=m.header)
+                if self.compressed is not None:
+                    im = self._compress(im)
                 out.append((im, detections_to_msg(d, m.header), d))
         self.frames += len(images)
         if self.metrics is not None:

@@ -471,6 +471,8 @@ class DataParallelDetector2D(_RingDP):
     :class:`~triton_client_amd.inference.engines.LocalDetector2D` (device path) or
     any engine with ``detect(frames)`` (host path, e.g. CPU)."""
 
+    compressed_out = False  # raw frames travel the ring: the drivers refuse compressed= for this engine
+
     def __init__(self, local, info: DistInfo, max_det: int = 300, monitor: Optional[HealthMonitor] = None,
                  nslots: int = 4, comm=None, arena_mb: Optional[int] = None):
         super().__init__(local, info, monitor, nslots, comm, arena_mb=arena_mb)
