@@ -96,6 +96,8 @@ def main():
     ap.add_argument("--lidar", type=int, default=512, help="PointCloud2 messages (0: skip)")
     ap.add_argument("--bev", action="store_true",
                     help="LiDAR side: also publish the bird's-eye-view Image of every cloud (RosInference3D bev_topic)")
+    ap.add_argument("--points", action="store_true",
+                    help="LiDAR side: also publish every cloud with its per-point labels (RosInference3D points_topic)")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -199,7 +201,8 @@ def main():
         st = _Stages()
         drv = RosInference3D(engine=eng3, params={"sub_topic": "/pc", "pub_topic": "/pc_out"}, bus=bus,
                              batch=a.batch, workers=a.workers, metrics=st, queue_size=window,
-                             bev_topic="/pc_bev" if a.bev else None)
+                             bev_topic="/pc_bev" if a.bev else None,
+                             **({"points_topic": "/pc_points"} if a.points else {}))
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout)
         st.sum.clear(), st.n.clear()
@@ -213,6 +216,8 @@ def main():
         if a.bev:
             v = drv.bev_view
             out["lidar"]["output"] += f" + bev Image {v.W}x{v.H} (host painter)"
+        if a.points:
+            out["lidar"]["output"] += " + labelled PointCloud2 (28 B per point)"
     bus.close()
     print(json.dumps(out), flush=True)
     if info is not None:

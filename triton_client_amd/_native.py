@@ -67,6 +67,10 @@ _KERNEL_SIGS = {
     # pred, gt, pred_cls, gt_cls, pred_off, gt_off, pair_off, tile_frame, tile_first, n_tiles, total_pairs,
     # iou_bev, iou_3d, stream
     "tca_box3d_iou": [P, P, P, P, P, P, P, P, P, I, L, P, P, P],
+    # data, frame_off, frame_n, B, max_n, point_step, off x/y/z/intensity, box_off, table, score, label, K, pt_off,
+    # owner, count, record, stream (csrc/kernels/points_in_boxes.hip)
+    "tca_points_in_boxes": [P, P, P, I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, P],
+    "tca_points_in_boxes_chunk": [],  # returns the boxes per LDS stage (not an error code)
     "tca_nms_merge": [P, P, P, P, P, P, P, P, I, I, I, F, I, I, P, P, P, P, P, P],
     "tca_pc2_unpack": [P, P, P, I, I, I, P, P, I, F, P, I, P, P, P, P],
     "tca_pc2_blocks_per_frame": [I],

@@ -21,6 +21,9 @@ def parse_args(argv=None):
     p.add_argument("--bev-out", default="", metavar="DIR",
                    help="save every cloud's bird's-eye-view picture (points + all detections) as DIR/NNNN.png")
     p.add_argument("--bev-res", type=float, default=0.1, metavar="M", help="metres per pixel of --bev-out")
+    p.add_argument("--points-topic", default="", metavar="TOPIC",
+                   help="write every cloud with its labels (x, y, z, intensity, label, instance, score per point) to "
+                        "the output bag on this topic")
     return p.parse_args(argv)
 
 
@@ -44,7 +47,8 @@ def main(argv=None) -> int:
                          batch=max(1, flags.frames_per_step), start_seq=flags.start_seq,
                          max_frames=flags.max_frames, verbose=flags.verbose, jsk=not flags.detection3d,
                          labels=labels_arg(flags.labels), score_thresh=flags.score_thresh,
-                         bev_out=flags.bev_out or None, bev_view=bev_view(engine, flags.bev_res, flags.bev_out))
+                         bev_out=flags.bev_out or None, bev_view=bev_view(engine, flags.bev_res, flags.bev_out),
+                         points_topic=flags.points_topic or None)
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

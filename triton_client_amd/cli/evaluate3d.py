@@ -28,6 +28,9 @@ def parse_args(argv=None):
     p.add_argument("--gt-z-offset", type=float, default=0.0,
                    help="added to the ground truth's z (0: ground truth in the sensor frame, like the engines' "
                         "boxes; only --metric 3d depends on it)")
+    p.add_argument("--min-gt-points", type=int, default=0, metavar="N",
+                   help="drop ground-truth boxes that contain fewer than N points of their cloud (the nuScenes rule; "
+                        "0: keep all)")
     p.add_argument("--eval-port", type=int, default=7658, help="Prometheus port (reference 7658; 0 = off)")
     p.add_argument("--json", default=None, help="write the summary here")
     return p.parse_args(argv)
@@ -60,7 +63,8 @@ def main(argv=None) -> int:
     ev =EvaluateInference3D(channel, client, engine=engine, params=params, metrics_port=flags.eval_port or None,
                              bus=default_bus(), metric=flags.metric, iouv=[float(v) for v in flags.iou.split(",")],
                              conf_thres=flags.conf_thres, gt_z_offset=flags.gt_z_offset,
-                             gt_type="detection3d" if flags.detection3d else "jsk", device=flags.device)
+                             gt_type="detection3d" if flags.detection3d else "jsk", device=flags.device,
+                             min_gt_points=flags.min_gt_points)
     if flags.bag:
         ev.evaluate_bag(flags.bag, batch=max(1, flags.frames_per_step))
     else:

@@ -17,6 +17,9 @@ def parse_args(argv=None):
     p.add_argument("--bev-topic", default="", metavar="TOPIC",
                    help="also publish an rgb8 Image of every cloud from above (points + all detections) here")
     p.add_argument("--bev-res", type=float, default=0.1, metavar="M", help="metres per pixel of --bev-topic")
+    p.add_argument("--points-topic", default="", metavar="TOPIC",
+                   help="also publish every cloud with its labels here: a PointCloud2 of x, y, z, intensity, label, "
+                        "instance (index into the box message), score per point")
     return p.parse_args(argv)
 
 
@@ -42,7 +45,8 @@ def main(argv=None) -> int:
                          labels=labels_arg(flags.labels), score_thresh=flags.score_thresh,
                          queue_size=None if flags.play else 50,
                          batch=flags.live_batch, workers=flags.live_workers, bev_topic=flags.bev_topic or None,
-                         bev_view=bev_view(engine, flags.bev_res, flags.bev_topic))
+                         bev_view=bev_view(engine, flags.bev_res, flags.bev_topic),
+                         points_topic=flags.points_topic or None)
     if flags.play:
         play_bag(flags.play, bus, topics=[params["sub_topic"]])
     drv.start_inference(spin=True, timeout=flags.spin_timeout)

@@ -109,7 +109,8 @@ class BagInference3D(RosInference3D):
                  bev_out: Optional[str] = None, **kw):
         """bev_out: a directory; every cloud's bird's-eye-view picture is saved there as
         ``NNNN.png`` (the naming of the 2D replay's ``out_dir``) and, with an output bag,
-        written to it on ``bev_topic`` (default ``<pub_topic>/bev``)."""
+        written to it on ``bev_topic`` (default ``<pub_topic>/bev``).  With ``points_topic`` the
+        labelled cloud of every input cloud is written to the output bag on that topic."""
         super().__init__(channel, client, **kw)
         self.bev_out = bev_out or None
         if self.bev_out and not self.bev_topic:
@@ -136,13 +137,16 @@ class BagInference3D(RosInference3D):
                     if not chunk:
                         break
                 for m, (out, pred, *pic) in zip(chunk, self.process(chunk)):
-                    if pic and self.bev_out:
-                        _save_png(os.path.join(self.bev_out, f"{count:04}.png"), pic[0])
+                    bev = pic[0] if pic else None
+                    if bev is not None and self.bev_out:
+                        _save_png(os.path.join(self.bev_out, f"{count:04}.png"), bev)
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
                         ob.write(p["pub_topic"], out)
-                        if pic:
-                            ob.write(self.bev_topic, pic[0])
+                        if bev is not None:
+                            ob.write(self.bev_topic, bev)
+                        if len(pic) > 1:
+                            ob.write(self.points_topic, pic[1])
                     if self.verbose:
                         print(m.header.seq)
                     self.results.append((m.header.seq, pred))

@@ -114,6 +114,32 @@ class Detector3D(ABC):
                                         names, zo))
         return out
 
+    def point_labeler(self):
+        """This engine's :class:`~triton_client_amd.ops.points_in_boxes.PointLabeler`: on the
+        engine's GPU when it has one (``device`` / ``label_device``), else on the host."""
+        lab = getattr(self, "_point_labeler", None)
+        if lab is None:
+            from ..ops.points_in_boxes import PointLabeler
+
+            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
+            lab = self._point_labeler = PointLabeler(dev)
+        return lab
+
+    def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
+                     idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
+        """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,
+        payload)`` against the boxes ``preds[b][idx_per_cloud[b]]`` (all of them without an
+        index), ``owner`` indexing that selection; ``payload`` is the labelled cloud's 28-byte
+        records (``ops.points_in_boxes``).  Points are the message's own x, y, z: the engines'
+        boxes are in the sensor frame."""
+        boxes, scores, labels = [], [], []
+        for b, p in enumerate(preds):
+            idx = slice(None) if idx_per_cloud is None else np.asarray(idx_per_cloud[b], np.int64)
+            boxes.append(np.asarray(p["pred_boxes"])[idx])
+            scores.append(np.asarray(p["pred_scores"])[idx])
+            labels.append(np.asarray(p["pred_labels"])[idx])
+        return Detector3D.point_labeler(self).label(clouds, boxes, scores, labels)  # (also for a duck-typed engine)
+
 
 def pack_task_segments(res, k: int, max_out: int):
     """CenterPointResult (NMS segments [B * T, mo, 9] internal box order, counts [B * T])
@@ -1086,6 +1112,7 @@ class RemoteDetector3D(_RemoteBase, Detector3D):
                 self.pre = type(self.pre)(self.pre.cfg, device)
         self.names = self.post.load_class_names()
         self.z_offset, self.normalize = z_offset, normalize_intensity
+        self.label_device = _device(device)  # where label_points runs (the client's GPU, if it has one)
         self.out_names = [o["name"] for o in self.outputs]
         ch = channel
         if ch.input is not None:

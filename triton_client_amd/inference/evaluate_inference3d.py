@@ -15,6 +15,15 @@ Ground truth is a jsk ``BoundingBoxArray`` (``label`` = class) or a
 ``vision_msgs/Detection3DArray`` (``results[0].id`` = class), i.e. what the live
 driver publishes: :func:`gt3d_from_msg` inverts ``jsk_columns`` /
 ``boxes_to_detection3d``.
+
+``min_gt_points=N`` (default 0: nothing changes) leaves out ground truth the sensor
+did not see, the nuScenes rule (``filter_eval_boxes`` drops boxes without LiDAR
+points; OpenPCDet's configs carry ``filter_by_min_points``): a ground-truth box
+that contains fewer than N points of its cloud is dropped before it reaches the
+evaluator; predictions are not filtered.  The counts come from
+:class:`..ops.points_in_boxes.PointLabeler` on the boxes after ``gt_z_offset``.
+Cloud and ground truth of a seq arrive in either order: whichever comes first is
+held (of a cloud only x, y, z) until the other is known.
 """
 from __future__ import annotations
 
@@ -70,7 +79,8 @@ class EvaluateInference3D(BaseInference):
     def __init__(self, channel=None, client=None, engine: Optional[Detector3D] = None, params: Optional[dict] = None,
                  bus=None, metrics_port: Optional[int] = 7658, metric: str = "bev",
                  iouv: Sequence[float] = IOU_THRESHOLDS_3D, conf_thres: float = 0.0, z_offset: float = 1.5,
-                 gt_z_offset: float = 0.0, gt_type: str = "jsk", device="auto", class_names=None):
+                 gt_z_offset: float = 0.0, gt_type: str = "jsk", device="auto", class_names=None,
+                 min_gt_points: int = 0):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset)
@@ -81,6 +91,9 @@ class EvaluateInference3D(BaseInference):
             raise ValueError(f"gt_type {gt_type!r}: 'jsk' or 'detection3d'")
         self.gt_msg_type = msgs.BoundingBoxArray if gt_type == "jsk" else msgs.Detection3DArray
         self.evaluator = DetectionEvaluator3D(metric=metric, iouv=np.asarray(iouv, np.float64), device=device)
+        self.min_gt_points, self.gt_dropped = max(0, int(min_gt_points)), 0
+        self._labeler, self._device = None, device
+        self._held_clouds, self._held_gts = {}, {}  # seq -> xyz cloud / ground truth waiting for the other
         self.metrics = None
         if metrics_port is not None:
             from ..utils.metrics import EvalMetrics
@@ -113,15 +126,42 @@ class EvaluateInference3D(BaseInference):
         d = self.engine.detect([msg])[0]
         with self._lock:
             self.evaluator.add_detections(seq, d, self.conf_thres)
+            if self.min_gt_points:
+                self._cloud_known(msg)
 
     def _add_gt(self, msg):
         seq, g = gt3d_from_msg(msg)
         g[:, 2] += self.gt_z_offset
-        self.evaluator.add_ground_truth(seq, g)
+        if not self.min_gt_points:
+            self.evaluator.add_ground_truth(seq, g)
+        elif seq in self._held_clouds:
+            self._add_seen_gt(seq, g, self._held_clouds.pop(seq))
+        else:
+            self._held_gts[seq] = g
+
+    def _cloud_known(self, msg):
+        """The cloud of a seq has arrived: filter its waiting ground truth, or keep its x, y, z."""
+        from ..ops.points_in_boxes import cloud_xyzi, xyz_cloud
+
+        seq = msg.header.seq
+        if seq in self._held_gts:
+            self._add_seen_gt(seq, self._held_gts.pop(seq), msg)
+        elif seq not in self.evaluator.gts:
+            self._held_clouds[seq] = xyz_cloud(cloud_xyzi(msg), msg.header)
+
+    def _add_seen_gt(self, seq, g, cloud):
+        """Ground truth with at least ``min_gt_points`` points of its cloud inside → the evaluator."""
+        if self._labeler is None:
+            from ..ops.points_in_boxes import PointLabeler
+
+            self._labeler = PointLabeler(self._device)
+        keep = self._labeler.count_points(cloud, g[:, :7]) >= self.min_gt_points
+        self.gt_dropped += int((~keep).sum())
+        self.evaluator.add_ground_truth(seq, g[keep])
 
     def gt_callback(self, msg):
         with self._lock:
-            if msg.header.seq in self.evaluator.gts:
+            if msg.header.seq in self.evaluator.gts or msg.header.seq in self._held_gts:
                 self.gt_processed = True
                 self._maybe_done()
                 return
@@ -152,6 +192,8 @@ class EvaluateInference3D(BaseInference):
     def _run(self, clouds):
         for m, d in zip(clouds, self.engine.detect(clouds)):
             self.evaluator.add_detections(m.header.seq, d, self.conf_thres)
+            if self.min_gt_points:
+                self._cloud_known(m)
 
     # ------------------------------------------------------------------ metrics
     def calculate_metrics(self) -> EvalSummary3D:
@@ -176,8 +218,15 @@ class EvaluateInference3D(BaseInference):
             if sub is not None:
                 sub.unregister()
         self.pc_sub = self.gt_sub = None
+        with self._lock:  # ground truth whose cloud never came: no prediction to score it against, kept as it is
+            for seq, g in self._held_gts.items():
+                self.evaluator.add_ground_truth(seq, g)
+            self._held_gts, self._held_clouds = {}, {}
         self.summary = self.calculate_metrics()
         return self.summary
 
     def as_dict(self) -> dict:
-        return self.summary.as_dict(self.class_names or None, self.label_base)
+        d = self.summary.as_dict(self.class_names or None, self.label_base)
+        if self.min_gt_points:
+            d["min_gt_points"], d["gt_dropped"] = self.min_gt_points, self.gt_dropped
+        return d

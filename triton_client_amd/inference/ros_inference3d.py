@@ -13,6 +13,14 @@ taken from the box's own dimension (index 6 for 7-d boxes, 8 for 9-d; A8).
 engine returned (whatever ``labels`` / ``score_thresh`` keep in the box
 message) as a labelled box, rendered by the host painter ``utils/bev.py``
 for every engine.
+
+``points_topic``: also publish, per cloud, the cloud itself with its labels — a
+``PointCloud2`` with the cloud's header, height, width and is_dense, every point
+in input order as a 28-byte record (x, y, z, intensity as sent; ``label`` int32:
+the owner's class, 0 for background; ``instance`` int32: the owner's position in
+the ``boxes`` / ``detections`` array of the box message of the same cloud, -1 for
+none; ``score`` float32, 0 for none).  The owner of a point is the published box
+with the highest score that contains it (``ops/points_in_boxes.py``).
 """
 from __future__ import annotations
 
@@ -88,13 +96,14 @@ class RosInference3D(BaseInference):
                  bus=None, jsk: bool = True, labels: Optional[Sequence[int]] = (2,), score_thresh: float = 0.5,
                  z_offset: float = 1.5, queue_size: Optional[int] = 50, metrics=None, mode: str = "sync",
                  wire: str = "raw", batch: int = 1, workers: int = 1, bev_topic: Optional[str] = None,
-                 bev_view=None):
+                 bev_view=None, points_topic: Optional[str] = None):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
         self.bev_topic, self.bev_view, self.bev_pub = None, None, None
         if bev_topic:
             self.enable_bev(bev_topic, bev_view)
+        self.points_topic, self.points_pub = points_topic or None, None
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
@@ -111,11 +120,12 @@ class RosInference3D(BaseInference):
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
         if self.bev_topic:
             self.bev_pub = compat.Publisher(self.bev_topic, msgs.Image, queue_size=1, bus=self.bus)
+        if self.points_topic:
+            self.points_pub = compat.Publisher(self.points_topic, msgs.PointCloud2, queue_size=1, bus=self.bus)
         cb, qs = self._pc_callback, self.queue_size
         if self.batch > 1 or self.workers > 1:
             from .batching import MicroBatchRunner
-            self.runner = MicroBatchRunner(lambda cs: [(r[0], r[2] if len(r) > 2 else None) for r in self.process(cs)],
-                                           self._publish,
+            self.runner = MicroBatchRunner(lambda cs: [self._item(r) for r in self.process(cs)], self._publish,
                                            batch=self.batch, workers=self.workers,
                                            capacity=max(self.queue_size or 0, 2 * self.batch * self.workers))
             cb, qs = self.runner.push, None
@@ -141,11 +151,18 @@ class RosInference3D(BaseInference):
         self.bev_topic = topic
         self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
 
+    @staticmethod
+    def _item(r: tuple) -> tuple:
+        """What is published of one ``process`` result: (box message, picture or None[, labelled cloud])."""
+        return (r[0],) + (tuple(r[2:]) if len(r) > 2 else (None,))
+
     def _publish(self, item) -> None:
-        m, im = item
+        m, im = item[0], item[1]
         self.pub.publish(m)
         if im is not None and self.bev_pub is not None:
             self.bev_pub.publish(im)
+        if len(item) > 2 and self.points_pub is not None:
+            self.points_pub.publish(item[2])
 
     def to_msg(self, pred: dict, header: msgs.Header):
         idx = select_boxes(pred, self.labels, self.score_thresh)
@@ -161,7 +178,8 @@ class RosInference3D(BaseInference):
 
     def process(self, clouds: Sequence[msgs.PointCloud2]) -> List[tuple]:
         """-> [(box message, prediction)] per cloud; with ``bev_topic``,
-        [(box message, prediction, bird's-eye-view Image)]."""
+        [(box message, prediction, bird's-eye-view Image)]; with ``points_topic``,
+        [(box message, prediction, bird's-eye-view Image or None, labelled PointCloud2)]."""
         t0 = time.perf_counter()
         timer = StageTimer(self.metrics)
         live = self._live()
@@ -180,12 +198,26 @@ class RosInference3D(BaseInference):
                                          is_bigendian=0, step=3 * view.W,
                                          data=memoryview(np.ascontiguousarray(f).reshape(-1))))
                        for (m, p), c, f in zip(out, clouds, pics)]
+        if self.points_topic:
+            with timer("points_label"):
+                out = self._with_points(clouds, preds, out)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
             self.metrics.frame(len(clouds))
         return out
 
+    def _with_points(self, clouds, preds, out: List[tuple]) -> List[tuple]:
+        """Each result with the labelled cloud as its fourth element: points labelled against the
+        boxes the box message carries, so ``instance`` indexes that message."""
+        from ..ops.points_in_boxes import labelled_cloud
+
+        idx = [select_boxes(p, self.labels, self.score_thresh) for p in preds]
+        fn = getattr(self.engine, "label_points", None)  # (an engine that is no Detector3D subclass)
+        res = fn(clouds, preds, idx) if fn is not None else Detector3D.label_points(self.engine, clouds, preds, idx)
+        return [(r[0], r[1], r[2] if len(r) > 2 else None, labelled_cloud(c, payload))
+                for r, c, (_, _, payload) in zip(out, clouds, res)]
+
     def _pc_callback(self, msg):
         for r in self.process([msg]):
-            self._publish((r[0], r[2] if len(r) > 2 else None))
+            self._publish(self._item(r))
