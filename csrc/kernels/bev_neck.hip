@@ -759,8 +759,9 @@ TCA_API int tca_bev_neck_head_x3p(int nbr, const void* const* x, const int* ldx,
   return neck_x3(nbr, x, ldx, offx, cin, s, w, bias, wh, bh, nh, out, ldo, B, H, W, grid, true, 0, stream);
 }
 
-// Same with the input storage as an argument (pair != 0: pair storage); variant: 0 (the one tiling,
-// also accepted as 3, its former number).
+// Same with the input storage as an argument (pair != 0: pair storage) and the tiling: variant 0
+// <8 waves, 2 stages>, 1 <8, 3>, 2 <4, 2> (128-pixel tiles, 2 * grid workgroups); the three give the
+// same bits.  Any other variant is refused (hipErrorInvalidValue).
 TCA_API int tca_bev_neck_head_x3v(int nbr, const void* const* x, const int* ldx, const int* offx, const int* cin,
                                   const int* s, const void* const* w, const float* const* bias, const void* wh,
                                   const float* bh, int nh, void* out, int ldo, int B, int H, int W, int grid,
