@@ -44,6 +44,29 @@ C3_FUSED = True
 FUSED_C3_WIDTHS = (16, 32, 64)  # c_ of the blocks c3_fused.hip takes
 
 
+def bev_out_pair(convs: Sequence[FusedConv], i: int) -> bool:
+    """Storage of conv i's output in a pair-storage BEV block: fp32 when the next conv, reading
+    fp32, is an F(2,3) layer and this conv's own kernel can write fp32, else pairs."""
+    if not WINO_F32_CHAIN or i + 1 >= len(convs):
+        return True
+    return not (convs[i + 1].route(False, False).family == "wino" and convs[i].route(True, False).out_fp32)
+
+
+def bev_first_conv_gated(cv: FusedConv) -> bool:
+    """The first conv, over a pair canvas with its occupancy bytes, loads only occupied cells."""
+    return cv.route(True, True, occ=True).gated
+
+
+def bev_uniform_eligible(convs: Sequence[FusedConv]) -> bool:
+    """The first block's convs take the kernels that skip uniform tiles: the stride-2 hx3 kernel
+    over the canvas (or s2sp, which computes every tile), then stride-1 hx3 or F(2,3) layers."""
+    if not 2 <= len(convs) <= 8:
+        return False
+    fams = [cv.route(i == 0 or bev_out_pair(convs, i - 1), bev_out_pair(convs, i), occ=i == 0).family
+            for i, cv in enumerate(convs)]
+    return fams[0] in ("hx3s2", "s2sp") and all(f in ("hx3", "wino") for f in fams[1:])
+
+
 def _fc(m: ConvBNAct, device, precision: str = "bf16", **kw) -> FusedConv:
     assert m.fused, "call fuse_model() first"
     return FusedConv(m.conv, act=m.act, device=device, precision=precision, **kw)
@@ -379,18 +402,11 @@ class _BEVBackbonePlan:
             self.depth = torch.zeros((B, H1, W1), dtype=torch.uint8, device=device)
 
     def out_pair(self, convs, i: int) -> bool:
-        """Storage of conv i's output in its block: fp32 when the next conv is an F(2,3) layer and
-        this conv can write fp32 (an F(2,3) layer, or the stride-2 hx3 kernel), else pairs."""
-        from ..ops import conv as conv_mod
-        if not (self.pair and WINO_F32_CHAIN and conv_mod.WINO) or i + 1 >= len(convs):
-            return True
-        cv, nxt = convs[i], convs[i + 1]
-        return not (nxt.wino_ok() and (cv.wino_ok() or (cv.s == 2 and cv.hx3_ok() and conv_mod.HX3S2)))
+        """Storage of conv i's output in its block (bev_out_pair)."""
+        return not self.pair or bev_out_pair(convs, i)
 
     def _uniform_eligible(self) -> bool:
-        convs = self.blocks[0][0]
-        return (self.pair and len(convs) >= 2 and convs[0].s == 2 and convs[0].hx3_ok()
-                and all(c.s == 1 and c.hx3_ok() for c in convs[1:]) and len(convs) <= 8)
+        return self.pair and bev_uniform_eligible(self.blocks[0][0])
 
     @torch.no_grad()
     def _uniform_values(self, device) -> Optional[List[torch.Tensor]]:
@@ -508,10 +524,8 @@ class FastBEV:
 
     def first_conv_gated(self) -> bool:
         """The plan's only reader of the pillar canvas is its first conv, and (pair storage with the
-        occupancy bytes) that conv loads only occupied cells: a non-transposed conv of at most 32
-        taps over pairs takes an occupancy-gated kernel (ops/conv.py: s2sp, hx3s2, x3p_occ)."""
-        cv = self.blocks[0][0][0]
-        return bool(self.pair and not cv.transpose and cv.k * cv.k <= 32)
+        occupancy bytes) that conv loads only occupied cells."""
+        return self.pair and bev_first_conv_gated(self.blocks[0][0][0])
 
     def forward(self, canvas: NHWC):
         if self.pair and not canvas.pair:

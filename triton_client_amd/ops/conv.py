@@ -97,37 +97,51 @@ def _ceil(x, m):
 
 
 PRECISIONS = ("fp32", "bf16")
-# split-product tiles with pair-storage instantiations (conv_mfma.hip launch_glds_x3p: global_load_lds
-# kernels 20-42, buffer-descriptor DMA kernels 68-79)
+# mirrors the switch in conv_mfma.hip launch_glds_x3p
 PAIR_TILES = (20, 22, 24, 25, 26, 32, 37, 41, 42, 68, 69, 70, 71, 72, 73, 74, 75, 76, 77, 78, 79, 90, 91, 92, 93, 94, 95, 96, 97, 102)
 
 
+# FusedConv.route decides which kernel takes a layer; it reads these switches on every call.
 # conv_hx3.hip (3x3 stride-1 / stride-2 pair convs with register-streamed fragment-order
 # weights): the default for every eligible layer (HX3 / HX3S2 False: the conv_mfma.hip tiles,
-# for A/B runs).  Tiles 110 (auto) and 111-116 (hx3_launch tiles 1-6) select the stride-1
-# kernel explicitly, 120 and 121-124 (hx3s2_launch tiles 1-4) the stride-2 one.
+# for A/B runs).
 HX3 = True
 HX3S2 = True
-HX3_TILES = (110, 111, 112, 113, 114, 115, 116)
-HX3S2_TILES = (120, 121, 122, 123, 124)
 # conv_wino.hip (3x3 stride-1 by 1-D Winograd F(2,3), 1.5x fewer MFMAs than hx3): the default for
-# every eligible stride-1 layer (WINO False: hx3).  Tiles 130 (auto) and 131-134 select it explicitly.
+# every eligible stride-1 layer (WINO False: hx3).
 WINO = os.environ.get("TCA_WINO", "1") != "0"  # TCA_WINO=0: hx3 for A/B runs
+WINO_MIN_N = int(os.environ.get("TCA_WINO_MIN_N", "128"))  # narrower layers stay on hx3 (A/B: profiles/r5/wino_ab.md)
 # conv_s2sp.hip (the sparse-gather stride-2 conv: only (pixel, tap) pairs whose input cell is
 # occupied) for a stride-2 pair conv over an occupancy-marked canvas with N == 64 and Cin 32 / 64
 # (the first PointPillars BEV conv).  Opt-in (S2SP True / TCA_S2SP=1): measured no faster than the
 # dense occupancy-masked hx3s2 kernel in the step (profiles/r5/s2sp/), which stays the default.
-# Tiles 140 (auto: 4 x 32 output tiles), 141 (8 x 32) and 142 (2 x 32) select it explicitly.
 S2SP = os.environ.get("TCA_S2SP", "0") == "1"
-S2SP_TILES = (140, 141, 142)
 S2SP_TILE = int(os.environ.get("TCA_S2SP_TILE", "0"))
-WINO_MIN_N = int(os.environ.get("TCA_WINO_MIN_N", "128"))  # narrower layers stay on hx3 (A/B: profiles/r5/wino_ab.md)
-WINO_TILES = (130, 131, 132, 133, 134)
 # sweep overrides of the auto tile choice (tools/gpu_knob_sweep.sh): hx3_launch / hx3s2_launch / wino_launch tile
 # numbers applied where the caller asked for tile 0; unset = the kernels' own choice
 HX3_TILE_AUTO = int(os.environ.get("TCA_HX3_TILE", "0"))
 HX3S2_TILE_AUTO = int(os.environ.get("TCA_HX3S2_TILE", "0"))
 WINO_TILE_AUTO = int(os.environ.get("TCA_WINO_TILE", "0"))
+# public tile= number -> (the family it asks for, that launcher's own tile number; 0: its auto choice):
+# hx3_launch 1-6, hx3s2_launch 1-4, wino_launch 1-4, s2sp 1 / 2 (8 x 32 / 2 x 32 output tiles; auto 4 x 32)
+TILES = {**{110 + t: ("hx3", t) for t in range(7)}, **{120 + t: ("hx3s2", t) for t in range(5)},
+         **{130 + t: ("wino", t) for t in range(5)}, **{140 + t: ("s2sp", t) for t in range(3)},
+         **{t: ("x3p", t) for t in PAIR_TILES}}
+# native entry of each family
+ENTRIES = {"bf16": "tca_conv_nhwc", "x3": "tca_conv_nhwc_x3", "x3p": "tca_conv_nhwc_x3p",
+           "x3p_occ": "tca_conv_nhwc_x3p_occ", "hx3": "tca_conv_hx3p", "hx3_uni": "tca_conv_hx3p_uni",
+           "hx3s2": "tca_conv_hx3s2p", "wino": "tca_conv_wino", "s2sp": "tca_conv_s2sp"}
+
+
+@dataclass(frozen=True)
+class Route:
+    """The kernel that takes one FusedConv call (FusedConv.route)."""
+    family: str  # a key of ENTRIES
+    tile: int  # the launcher's own tile number
+    # wino, hx3s2 or s2sp asked for plain fp32 storage out, which an F(2,3) layer reads without
+    # the pair join (x3p takes out_pair=0 too, but the plans keep pairs behind it)
+    out_fp32: bool = False
+    gated: bool = False  # reads only the pixels marked in occ
 
 
 def wino_tile(H: int, W: int, N: int) -> int:
@@ -256,6 +270,7 @@ class FusedConv:
         self.b_gemm = self.bias.to(self.device).contiguous()
         # fragment-order weights of the hx3 kernel (built here, never inside a graph capture)
         self._w_frag = frag_weights(W).to(self.device) if self.hx3_ok() and self.device.type == "cuda" else None
+        self._w_wino = {}  # F(2,3) weight image per orientation, built on first use
         # fp32 copies for the CPU path
         self.w_f32, self.b_f32 = w, b
 
@@ -282,109 +297,110 @@ class FusedConv:
         for t in (x.t, out.t) + ((res.t,) if res is not None else ()):
             if t.dtype != self.dtype:
                 raise TypeError(f"{self.precision} conv needs {self.dtype} activations, got {t.dtype}")
-        gh, gw = (H, W) if self.transpose else (Ho, Wo)
+        r = self.route(x.pair, out.pair, None if res is None else "pair" if res.pair else "fp32",
+                       x.occ is not None, uni is not None, tile, H, W)
         act = self.act | (16 if (self.post_res and res is not None) else 0)
-        rp = (_native.ptr(res.t if res is not None else None), res.t.shape[-1] if res is not None else 0,
-              res.off if res is not None else 0)
-        if (x.occ is None and res is None and self.wino_ok() and not self.transpose and
-                (tile in WINO_TILES or (tile == 0 and WINO))):
-            # F(2,3) stride-1 kernel: pair or fp32 storage on either side
-            return self._wino(x, out, tile, stream, uni)
-        if x.pair or out.pair:
-            # pair storage: the global_load_lds split-product kernels (Cin % 32, K == Kp)
-            if self.precision != "fp32" or not x.pair or (res is not None and res.pair != out.pair):
-                raise TypeError("pair activations: fp32 convs reading pairs (output pairs or fp32)")
-            if (res is None and x.occ is not None and self.s2sp_ok() and
-                    (tile in S2SP_TILES or (tile == 0 and S2SP))):
-                assert x.occ.dtype == torch.uint8 and tuple(x.occ.shape) == (B, H, W), (x.occ.shape, (B, H, W))
-                _native.call("tca_conv_s2sp", _native.ptr(x.t), B, H, W, self.cin_p, x.t.shape[-1], x.off,
-                             _native.ptr(self.hx3_weights()), _native.ptr(self.b_gemm), self.N,
-                             _native.ptr(out.t), out.t.shape[-1], out.off, self.act | (0 if out.pair else 32),
-                             _native.ptr(x.occ), tile - 140 if tile in S2SP_TILES else S2SP_TILE,
-                             _native.stream_ptr(stream))
-                return out
-            if ((out.pair or res is None) and self.hx3_ok() and self.s == 2 and
-                    (tile in HX3S2_TILES or (tile == 0 and HX3S2))):
-                occ = x.occ
-                if occ is not None:
-                    assert occ.dtype == torch.uint8 and tuple(occ.shape) == (B, H, W), (occ.shape, (B, H, W))
-                # act | 32: fp32 storage out (the input of an F(2,3) layer)
-                _native.call("tca_conv_hx3s2p", _native.ptr(x.t), B, H, W, self.cin_p, x.t.shape[-1], x.off,
-                             _native.ptr(self.hx3_weights()), _native.ptr(self.b_gemm), self.N,
-                             _native.ptr(out.t), out.t.shape[-1], out.off, act | (0 if out.pair else 32), *rp,
-                             _native.ptr(occ), *self._uni_args(uni, B, Ho, Wo, res),
-                             tile - 120 if tile in HX3S2_TILES else HX3S2_TILE_AUTO, _native.stream_ptr(stream))
-                return out
-            if (out.pair and x.occ is None and self.hx3_ok() and self.s == 1 and
-                    (tile in HX3_TILES or (tile == 0 and HX3))):
-                if uni is not None and res is None:
-                    depth, dmin, val = uni
-                    assert depth.dtype == torch.uint8 and tuple(depth.shape) == (B, Ho, Wo), depth.shape
-                    assert val.dtype == torch.float32 and val.numel() == self.N, (val.dtype, val.shape)
-                    _native.call("tca_conv_hx3p_uni", _native.ptr(x.t), B, H, W, self.cin_p, x.t.shape[-1], x.off,
-                                 _native.ptr(self.hx3_weights()), _native.ptr(self.b_gemm), self.N,
-                                 _native.ptr(out.t), out.t.shape[-1], out.off, act, _native.ptr(depth), dmin,
-                                 _native.ptr(val), tile - 110 if tile in HX3_TILES else HX3_TILE_AUTO,
-                                 _native.stream_ptr(stream))
-                    return out
-                _native.call("tca_conv_hx3p", _native.ptr(x.t), B, H, W, self.cin_p, x.t.shape[-1], x.off,
-                             _native.ptr(self.hx3_weights()), _native.ptr(self.b_gemm), self.N,
-                             _native.ptr(out.t), out.t.shape[-1], out.off, act, *rp,
-                             tile - 110 if tile in HX3_TILES else HX3_TILE_AUTO, _native.stream_ptr(stream))
-                return out
-            args = (_native.ptr(x.t), B, H, W, self.cin_p, x.t.shape[-1], x.off, _native.ptr(self.w_gemm),
-                    _native.ptr(self.b_gemm), self.N, self.k, self.k, self.s, self.p, self.Kp, _native.ptr(out.t), gh,
-                    gw, out.t.shape[-1], out.off, act, *rp, self.shuffle, tile if tile in PAIR_TILES else 0,
-                    int(out.pair))
-            if x.occ is not None and not self.transpose:
-                assert x.occ.dtype == torch.uint8 and tuple(x.occ.shape) == (B, H, W), (x.occ.shape, (B, H, W))
-                _native.call("tca_conv_nhwc_x3p_occ", *args, _native.ptr(x.occ), _native.stream_ptr(stream))
-            else:
-                _native.call("tca_conv_nhwc_x3p", *args, _native.stream_ptr(stream))
-            return out
-        fn = "tca_conv_nhwc_x3" if self.precision == "fp32" else "tca_conv_nhwc"
-        _native.call(fn, _native.ptr(x.t), B, H, W, self.cin_p, x.t.shape[-1], x.off,
-                     _native.ptr(self.w_gemm), _native.ptr(self.b_gemm), self.N, self.k, self.k, self.s, self.p,
-                     self.Kp, _native.ptr(out.t), gh, gw, out.t.shape[-1], out.off, act, *rp, self.shuffle, tile,
-                     _native.stream_ptr(stream))
+        getattr(self, "_" + r.family)(r, x, out, res, act, uni, _native.stream_ptr(stream))
         return out
+
+    def route(self, x_pair: bool, out_pair: bool, res: Optional[str] = None, occ: bool = False, uni: bool = False,
+              tile: int = 0, H: int = 0, W: int = 0) -> Route:
+        """The kernel that takes this conv, from plain values: input / output storage, the residual's
+        (None / "pair" / "fp32"), whether x carries occupancy bytes and the call a uniform-tile
+        skip, the public tile number, the input H, W (only the wino tile depends on them).  An
+        explicit tile asks for its family (TILES) whatever the switches say, tile 0 follows them; a
+        family that cannot take the call passes it on: wino, then s2sp, hx3s2, hx3, x3p over pairs."""
+        assert res in (None, "pair", "fp32"), res
+        fam, t = TILES.get(tile, (None, 0))
+        if (not occ and res is None and self.wino_ok()) and (fam == "wino" or (tile == 0 and WINO)):
+            # F(2,3) stride-1 kernel: pair or fp32 storage on either side
+            return Route("wino", (t if fam == "wino" else 0) or WINO_TILE_AUTO or wino_tile(H, W, self.N),
+                         out_fp32=not out_pair)
+        if not (x_pair or out_pair):
+            return Route("x3" if self.precision == "fp32" else "bf16", tile)
+        # pair storage: the global_load_lds split-product kernels (Cin % 32, K == Kp)
+        if self.precision != "fp32" or not x_pair or (res is not None and (res == "pair") != out_pair):
+            raise TypeError("pair activations: fp32 convs reading pairs (output pairs or fp32)")
+        if (res is None and occ and self.s2sp_ok()) and (fam == "s2sp" or (tile == 0 and S2SP)):
+            return Route("s2sp", t if fam == "s2sp" else S2SP_TILE, out_fp32=not out_pair, gated=True)
+        if ((out_pair or res is None) and self.hx3_ok() and self.s == 2) and (fam == "hx3s2" or (tile == 0 and HX3S2)):
+            return Route("hx3s2", t if fam == "hx3s2" else HX3S2_TILE_AUTO, out_fp32=not out_pair, gated=occ)
+        if (out_pair and not occ and self.hx3_ok() and self.s == 1) and (fam == "hx3" or (tile == 0 and HX3)):
+            return Route("hx3_uni" if uni and res is None else "hx3", t if fam == "hx3" else HX3_TILE_AUTO)
+        gate = occ and not self.transpose
+        # conv_mfma.hip tca_conv_nhwc_x3p_occ drops occ for more than 32 taps
+        return Route("x3p_occ" if gate else "x3p", t if fam == "x3p" else 0, gated=gate and self.k * self.k <= 32)
 
     def hx3_ok(self) -> bool:
         """conv_hx3.hip takes this conv: fp32, 3x3 stride 1 or 2, pad 1, Cin % 32, N % 64."""
         return (self.precision == "fp32" and not self.transpose and self.k == 3 and self.s in (1, 2) and self.p == 1
                 and self.cin_p % 32 == 0 and self.K == self.Kp and self.N % 64 == 0)
 
-    def _uni_args(self, uni, B, Ho, Wo, res=None):
-        """(depth, uni_min, value) pointers of an optional uniform-tile skip (see _BEVBackbonePlan)."""
-        if uni is None or res is not None:
-            return None, 0, None
-        depth, dmin, val = uni
-        assert depth.dtype == torch.uint8 and tuple(depth.shape) == (B, Ho, Wo), depth.shape
-        assert val.dtype == torch.float32 and val.numel() == self.N, (val.dtype, val.shape)
-        return _native.ptr(depth), dmin, _native.ptr(val)
-
     def wino_ok(self) -> bool:
         """conv_wino.hip takes this conv: hx3's shapes at stride 1, ReLU or no activation."""
         return self.hx3_ok() and self.s == 1 and self.act in (ACT_NONE, ACT_RELU) and self.N >= WINO_MIN_N
 
-    def _wino(self, x: NHWC, out: NHWC, tile: int, stream, uni) -> NHWC:
-        B, H, W, _ = x.shape
-        t = tile - 130 if tile in WINO_TILES[1:] else (WINO_TILE_AUTO or wino_tile(H, W, self.N))
-        cm = t in (2, 4)
-        if not hasattr(self, "_w_wino"):
-            self._w_wino = {}
+    @staticmethod
+    def _in_args(x: NHWC):
+        B, H, W, C = x.shape
+        return _native.ptr(x.t), B, H, W, C, x.t.shape[-1], x.off
+
+    @staticmethod
+    def _res_args(res: Optional[NHWC]):
+        return (_native.ptr(res.t), res.t.shape[-1], res.off) if res is not None else (_native.ptr(None), 0, 0)
+
+    @staticmethod
+    def _occ_ptr(x: NHWC) -> int:
+        if x.occ is not None:
+            assert x.occ.dtype == torch.uint8 and tuple(x.occ.shape) == tuple(x.shape[:3]), (x.occ.shape, x.shape)
+        return _native.ptr(x.occ)
+
+    def _uni_args(self, uni, x: NHWC):
+        """(depth, uni_min, value) of an optional uniform-tile skip (see _BEVBackbonePlan)."""
+        if uni is None:
+            return _native.ptr(None), 0, _native.ptr(None)
+        depth, dmin, val = uni
+        assert depth.dtype == torch.uint8 and tuple(depth.shape) == (x.shape[0], *self.out_hw(*x.shape[1:3])), depth.shape
+        assert val.dtype == torch.float32 and val.numel() == self.N, (val.dtype, val.shape)
+        return _native.ptr(depth), dmin, _native.ptr(val)
+
+    # one launch method per family: _<family>(route, x, out, res, act, uni, stream pointer)
+    def _x3(self, r, x, out, res, act, uni, stream):
+        H, W = x.shape[1:3]
+        gh, gw = (H, W) if self.transpose else self.out_hw(H, W)
+        tail = {"x3p": (int(out.pair),), "x3p_occ": (int(out.pair), self._occ_ptr(x))}.get(r.family, ())
+        _native.call(ENTRIES[r.family], *self._in_args(x), _native.ptr(self.w_gemm), _native.ptr(self.b_gemm), self.N,
+                     self.k, self.k, self.s, self.p, self.Kp, _native.ptr(out.t), gh, gw, out.t.shape[-1], out.off, act,
+                     *self._res_args(res), self.shuffle, r.tile, *tail, stream)
+
+    _bf16 = _x3p = _x3p_occ = _x3
+
+    def _hx_args(self, x, out, act):
+        # act | 32: fp32 storage out (the input of an F(2,3) layer)
+        return (*self._in_args(x), _native.ptr(self.hx3_weights()), _native.ptr(self.b_gemm), self.N,
+                _native.ptr(out.t), out.t.shape[-1], out.off, act | (0 if out.pair else 32))
+
+    def _s2sp(self, r, x, out, res, act, uni, stream):
+        _native.call(ENTRIES[r.family], *self._hx_args(x, out, act), self._occ_ptr(x), r.tile, stream)
+
+    def _hx3s2(self, r, x, out, res, act, uni, stream):
+        _native.call(ENTRIES[r.family], *self._hx_args(x, out, act), *self._res_args(res), self._occ_ptr(x),
+                     *self._uni_args(uni if res is None else None, x), r.tile, stream)
+
+    def _hx3(self, r, x, out, res, act, uni, stream):
+        mid = self._uni_args(uni, x) if r.family == "hx3_uni" else self._res_args(res)
+        _native.call(ENTRIES[r.family], *self._hx_args(x, out, act), *mid, r.tile, stream)
+
+    _hx3_uni = _hx3
+
+    def _wino(self, r, x, out, res, act, uni, stream):
+        cm = r.tile in (2, 4)
         wf = self._w_wino.get(cm)
         if wf is None:  # built on first use, never inside a graph capture (the plans warm up first)
             wf = self._w_wino[cm] = wino_weights(self.w_f32_gemm, self.cin_p, cm).to(self.device)
-        depth, dmin, val = uni if uni is not None else (None, 0, None)
-        if uni is not None:
-            assert depth.dtype == torch.uint8 and tuple(depth.shape) == (B, H, W), depth.shape
-            assert val.dtype == torch.float32 and val.numel() == self.N, (val.dtype, val.shape)
-        _native.call("tca_conv_wino", _native.ptr(x.t), B, H, W, self.cin_p, x.t.shape[-1], x.off, int(x.pair),
-                     _native.ptr(wf), _native.ptr(self.b_gemm), self.N, _native.ptr(out.t), out.t.shape[-1], out.off,
-                     int(out.pair), self.act, _native.ptr(depth), dmin, _native.ptr(val), t,
-                     _native.stream_ptr(stream))
-        return out
+        _native.call(ENTRIES[r.family], *self._in_args(x), int(x.pair), _native.ptr(wf), _native.ptr(self.b_gemm),
+                     self.N, _native.ptr(out.t), out.t.shape[-1], out.off, int(out.pair), act,
+                     *self._uni_args(uni, x), r.tile, stream)
 
     def hx3_weights(self) -> torch.Tensor:
         if self._w_frag is None:
