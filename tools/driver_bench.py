@@ -215,7 +215,10 @@ def main():
                         "output": "jsk BoundingBoxArray (label 2, score > 0.5)", "stages": st.summary()}
         if a.bev:
             v = drv.bev_view
-            out["lidar"]["output"] += f" + bev Image {v.W}x{v.H} (host painter)"
+            from triton_client_amd.inference.engines import Detector3D
+            painter = {"device": "tca_bev_render", "host": "host painter"}[Detector3D.bev_painter(eng3)]
+            out["lidar"]["output"] += f" + bev Image {v.W}x{v.H} ({painter})"
+            out["lidar"]["bev_painter"] = painter
         if a.points:
             out["lidar"]["output"] += " + labelled PointCloud2 (28 B per point)"
     bus.close()

@@ -71,6 +71,10 @@ _KERNEL_SIGS = {
     # owner, count, record, stream (csrc/kernels/points_in_boxes.hip)
     "tca_points_in_boxes": [P, P, P, I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, P],
     "tca_points_in_boxes_chunk": [],  # returns the boxes per LDS stage (not an error code)
+    # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z/intensity (-1: dense rows), x1, y1,
+    # inv_res, z0, zscale, z_offset, H, W, plane, box_off, table, K, text, text bytes, out, frame stride, row stride,
+    # stream (csrc/kernels/bev_render.hip)
+    "tca_bev_render": [P, L, P, P, I, I, I, I, I, I, I, F, F, F, F, F, F, I, I, P, P, P, I, P, I, P, L, I, P],
     "tca_nms_merge": [P, P, P, P, P, P, P, P, I, I, I, F, I, I, P, P, P, P, P, P],
     "tca_pc2_unpack": [P, P, P, I, I, I, P, P, I, F, P, I, P, P, P, P],
     "tca_pc2_blocks_per_frame": [I],

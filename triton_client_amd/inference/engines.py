@@ -100,19 +100,43 @@ class Detector3D(ABC):
         """PointCloud2 messages → per-cloud {pred_boxes, pred_scores, pred_labels}."""
 
     def render_bev(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict], view) -> List[np.ndarray]:
-        """The bird's-eye-view picture of each cloud and its predictions with the host painter
-        (``utils.bev.render_bev_frame``), from the points as this engine preprocesses them."""
+        """The bird's-eye-view picture of each cloud and its predictions, from the points as this
+        engine preprocesses them: painted by the engine's :meth:`bev_renderer` on its GPU when it
+        has one, else (and with ``TCA_DEVICE_BEV=0``) by the host painter
+        ``utils.bev.render_bev_frame``.  The two give the same bytes."""
         from ..ros.compat import cloud_to_numpy
         from ..utils.bev import label_names, render_bev_frame
 
         zo = float(getattr(self, "z_offset", 0.0))
         names = label_names(getattr(self, "names", None) or [], getattr(self, "label_base", 1))
+        if Detector3D.bev_painter(self) == "device":
+            return Detector3D.bev_renderer(self).render(clouds, preds, view, names, zo)
         out = []
         for c, p in zip(clouds, preds):
             pts = cloud_to_numpy(c, normalize_intensity=getattr(self, "normalize", True), z_offset=zo)
             out.append(render_bev_frame(pts, None, p["pred_boxes"], p["pred_scores"], p["pred_labels"], None, view,
                                         names, zo))
         return out
+
+    def bev_painter(self) -> str:
+        """``"device"`` when :meth:`render_bev` paints with ``tca_bev_render`` on this engine's
+        GPU (``label_device`` / ``device``), ``"host"`` for an engine without one (the ring
+        data-parallel engines among them) and with ``TCA_DEVICE_BEV=0``."""
+        from ..ops.bev import device_enabled
+
+        dev = getattr(self, "label_device", None) or getattr(self, "device", None)
+        return "device" if dev is not None and torch.device(dev).type == "cuda" and device_enabled() else "host"
+
+    def bev_renderer(self):
+        """This engine's :class:`~triton_client_amd.ops.bev.BevRenderer`, made once like
+        :meth:`point_labeler`."""
+        ren = getattr(self, "_bev_renderer", None)
+        if ren is None:
+            from ..ops.bev import BevRenderer
+
+            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
+            ren = self._bev_renderer = BevRenderer(dev)
+        return ren
 
     def point_labeler(self):
         """This engine's :class:`~triton_client_amd.ops.points_in_boxes.PointLabeler`: on the

@@ -11,8 +11,9 @@ taken from the box's own dimension (index 6 for 7-d boxes, 8 for 9-d; A8).
 ``bev_topic``: also publish, per cloud and with the cloud's header, an rgb8
 ``Image`` of the frame from above — points grey by height, every detection the
 engine returned (whatever ``labels`` / ``score_thresh`` keep in the box
-message) as a labelled box, rendered by the host painter ``utils/bev.py``
-for every engine.
+message) as a labelled box.  ``utils/bev.py`` defines the picture; an engine
+with a GPU paints the same bytes with ``tca_bev_render`` (``ops/bev.py``;
+``TCA_DEVICE_BEV=0``: the host painter).
 
 ``points_topic``: also publish, per cloud, the cloud itself with its labels — a
 ``PointCloud2`` with the cloud's header, height, width and is_dense, every point
