@@ -98,6 +98,9 @@ def main():
                     help="LiDAR side: also publish the bird's-eye-view Image of every cloud (RosInference3D bev_topic)")
     ap.add_argument("--points", action="store_true",
                     help="LiDAR side: also publish every cloud with its per-point labels (RosInference3D points_topic)")
+    ap.add_argument("--tracks", action="store_true",
+                    help="LiDAR side: also track the detections and publish the boxes with their track ids "
+                         "(RosInference3D tracks_topic; the clouds are stamped 0.1 s apart)")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -194,7 +197,8 @@ def main():
         msgs_in = []
         for i in range(warm + a.lidar):
             c = clouds[i % 8]
-            msgs_in.append(msgs.PointCloud2(header=msgs.Header(seq=i + 1, frame_id="os"), height=c.height,
+            msgs_in.append(msgs.PointCloud2(header=msgs.Header(seq=i + 1, stamp=msgs.Time(100 + i // 10, i % 10 * 10 ** 8),
+                                                               frame_id="os"), height=c.height,
                                             width=c.width, fields=c.fields, is_bigendian=False,
                                             point_step=c.point_step, row_step=c.row_step, data=c.data,
                                             is_dense=True))
@@ -202,7 +206,8 @@ def main():
         drv = RosInference3D(engine=eng3, params={"sub_topic": "/pc", "pub_topic": "/pc_out"}, bus=bus,
                              batch=a.batch, workers=a.workers, metrics=st, queue_size=window,
                              bev_topic="/pc_bev" if a.bev else None,
-                             **({"points_topic": "/pc_points"} if a.points else {}))
+                             **({"points_topic": "/pc_points"} if a.points else {}),
+                             **({"tracks_topic": "/pc_tracks"} if a.tracks else {}))
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout)
         st.sum.clear(), st.n.clear()
@@ -221,6 +226,13 @@ def main():
             out["lidar"]["bev_painter"] = painter
         if a.points:
             out["lidar"]["output"] += " + labelled PointCloud2 (28 B per point)"
+        if a.tracks:
+            trk = drv.tracker()
+            ts = trk.state()
+            out["lidar"]["output"] += f" + tracks ({trk.kind})"
+            out["lidar"]["tracker"] = trk.kind
+            out["lidar"]["tracks"] = {"frames": trk.frames, "ids_given": int(ts.next_id) - 1,
+                                      "live": int((ts.id != 0).sum()), "overflow": int(ts.overflow)}
     bus.close()
     print(json.dumps(out), flush=True)
     if info is not None:

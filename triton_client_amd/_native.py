@@ -75,6 +75,9 @@ _KERNEL_SIGS = {
     # inv_res, z0, zscale, z_offset, H, W, plane, box_off, table, K, text, text bytes, out, frame stride, row stride,
     # stream (csrc/kernels/bev_render.hip)
     "tca_bev_render": [P, L, P, P, I, I, I, I, I, I, I, F, F, F, F, F, F, I, I, P, P, P, I, P, I, P, L, I, P],
+    # rows, det_off (host), F, dt, reset, max_dist2, gates, state, capacity, max_age, alpha, out, stream
+    # (csrc/kernels/track3d.hip)
+    "tca_track3d": [P, P, I, P, P, P, I, P, I, I, F, P, P],
     "tca_nms_merge": [P, P, P, P, P, P, P, P, I, I, I, F, I, I, P, P, P, P, P, P],
     "tca_pc2_unpack": [P, P, P, I, I, I, P, P, I, F, P, I, P, P, P, P],
     "tca_pc2_blocks_per_frame": [I],

@@ -5,8 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_framework_flags, add_reference_flags, bev_view, labels_arg, load_params,
-                     setup_logging)
+from .common import (DATA, add_framework_flags, add_reference_flags, add_track_flags, bev_view, labels_arg,
+                     load_params, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -24,6 +24,8 @@ def parse_args(argv=None):
     p.add_argument("--points-topic", default="", metavar="TOPIC",
                    help="write every cloud with its labels (x, y, z, intensity, label, instance, score per point) to "
                         "the output bag on this topic")
+    add_track_flags(p, "write the boxes of every cloud, with their track ids in place of their classes, to the "
+                       "output bag on this topic")
     return p.parse_args(argv)
 
 
@@ -48,7 +50,8 @@ def main(argv=None) -> int:
                          max_frames=flags.max_frames, verbose=flags.verbose, jsk=not flags.detection3d,
                          labels=labels_arg(flags.labels), score_thresh=flags.score_thresh,
                          bev_out=flags.bev_out or None, bev_view=bev_view(engine, flags.bev_res, flags.bev_out),
-                         points_topic=flags.points_topic or None)
+                         points_topic=flags.points_topic or None, tracks_topic=flags.tracks_topic or None,
+                         track_options=track_options(flags))
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

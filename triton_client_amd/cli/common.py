@@ -158,6 +158,27 @@ def labels_arg(s: str):
     return None if s in ("all", "", "none") else tuple(int(v) for v in s.split(","))
 
 
+def add_track_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--tracks-topic, --track-max-age, --track-max-dist (``ops/track3d.py``)."""
+    p.add_argument("--tracks-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--track-max-age", type=int, default=3, metavar="FRAMES",
+                   help="a track missed this many clouds in a row still comes back with its id")
+    p.add_argument("--track-max-dist", default="", metavar="M | NAME=M,...",
+                   help="association gate in metres: one number for every class, or by class name (Car=4,"
+                        "Pedestrian=1; default 2, CenterPoint: the paper's nuScenes table)")
+
+
+def track_options(flags) -> dict:
+    """The ``track_options`` of the --track-* flags."""
+    from ..ops.track3d import parse_max_dist
+
+    opts = {"max_age": flags.track_max_age}
+    md = parse_max_dist(flags.track_max_dist)
+    if md is not None:
+        opts["max_dist"] = md
+    return opts
+
+
 def bev_view(engine, res: float, enabled):
     """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
     range for an engine that does not know its model's) at ``res`` metres per pixel; None

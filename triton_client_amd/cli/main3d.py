@@ -5,8 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_framework_flags, add_reference_flags, bev_view, labels_arg, load_params, play_bag,
-                     setup_logging)
+from .common import (DATA, add_framework_flags, add_reference_flags, add_track_flags, bev_view, labels_arg,
+                     load_params, play_bag, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -20,6 +20,7 @@ def parse_args(argv=None):
     p.add_argument("--points-topic", default="", metavar="TOPIC",
                    help="also publish every cloud with its labels here: a PointCloud2 of x, y, z, intensity, label, "
                         "instance (index into the box message), score per point")
+    add_track_flags(p, "also publish the boxes of every cloud here with their track ids in place of their classes")
     return p.parse_args(argv)
 
 
@@ -46,7 +47,8 @@ def main(argv=None) -> int:
                          queue_size=None if flags.play else 50,
                          batch=flags.live_batch, workers=flags.live_workers, bev_topic=flags.bev_topic or None,
                          bev_view=bev_view(engine, flags.bev_res, flags.bev_topic),
-                         points_topic=flags.points_topic or None)
+                         points_topic=flags.points_topic or None, tracks_topic=flags.tracks_topic or None,
+                         track_options=track_options(flags))
     if flags.play:
         play_bag(flags.play, bus, topics=[params["sub_topic"]])
     drv.start_inference(spin=True, timeout=flags.spin_timeout)

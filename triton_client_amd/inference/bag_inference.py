@@ -110,7 +110,8 @@ class BagInference3D(RosInference3D):
         """bev_out: a directory; every cloud's bird's-eye-view picture is saved there as
         ``NNNN.png`` (the naming of the 2D replay's ``out_dir``) and, with an output bag,
         written to it on ``bev_topic`` (default ``<pub_topic>/bev``).  With ``points_topic`` the
-        labelled cloud of every input cloud is written to the output bag on that topic."""
+        labelled cloud of every input cloud is written to the output bag on that topic, and with
+        ``tracks_topic`` the tracks message (the clouds are tracked in bag order)."""
         super().__init__(channel, client, **kw)
         self.bev_out = bev_out or None
         if self.bev_out and not self.bev_topic:
@@ -136,7 +137,10 @@ class BagInference3D(RosInference3D):
                     chunk = chunk[: max(0, self.max_frames - count)]
                     if not chunk:
                         break
-                for m, (out, pred, *pic) in zip(chunk, self.process(chunk)):
+                res = self.process(chunk)
+                if self.tracks_topic:
+                    res = self.track(res)
+                for m, (out, pred, *pic) in zip(chunk, res):
                     bev = pic[0] if pic else None
                     if bev is not None and self.bev_out:
                         _save_png(os.path.join(self.bev_out, f"{count:04}.png"), bev)
@@ -145,8 +149,10 @@ class BagInference3D(RosInference3D):
                         ob.write(p["pub_topic"], out)
                         if bev is not None:
                             ob.write(self.bev_topic, bev)
-                        if len(pic) > 1:
+                        if len(pic) > 1 and pic[1] is not None:
                             ob.write(self.points_topic, pic[1])
+                        if len(pic) > 2:
+                            ob.write(self.tracks_topic, pic[2])
                     if self.verbose:
                         print(m.header.seq)
                     self.results.append((m.header.seq, pred))

@@ -18,7 +18,10 @@ subscriber callback only enqueues:
   (tickets are handed out atomically with the take), and a result whose
   ``header.seq`` is not newer than the last one published is dropped, so the
   published stream's ``header.seq`` is strictly increasing whatever order
-  the batches finish in.
+  the batches finish in.  An optional ``ordered_fn`` is the stage that must see
+  the stream in order (a tracker): called once per ticket, in ticket order,
+  under the re-publisher's lock, with that ticket's items that survived the
+  stale-seq filter, it returns the items to publish.
 """
 from __future__ import annotations
 
@@ -64,10 +67,16 @@ class LatestWinsWindow:
 
 class OrderedRepublisher:
     """submit(ticket, [(seq, item), ...]) → publish_fn(item) in ticket order,
-    dropping items whose seq is not newer than the last published one."""
+    dropping items whose seq is not newer than the last published one.  With an
+    ``ordered_fn`` the surviving items of a ticket go through it first (one call per
+    ticket, in ticket order, under the lock) and what it returns is published; an
+    exception it raises is kept in ``errors`` and that ticket publishes nothing."""
 
-    def __init__(self, publish_fn: Callable):
+    def __init__(self, publish_fn: Callable, ordered_fn: Optional[Callable[[List], List]] = None,
+                 errors: Optional[List[BaseException]] = None):
         self.publish_fn = publish_fn
+        self.ordered_fn = ordered_fn
+        self.errors: List[BaseException] = errors if errors is not None else []
         self.next = 0
         self.pending: Dict[int, Sequence] = {}
         self.lock = threading.Lock()
@@ -79,6 +88,10 @@ class OrderedRepublisher:
         with self.lock:
             self.pending[ticket] = items
             while self.next in self.pending:
+                if self.ordered_fn is not None:
+                    self._release_ordered(self.pending.pop(self.next))
+                    self.next += 1
+                    continue
                 for seq, item in self.pending.pop(self.next):
                     if seq is not None and self.last_seq is not None and seq <= self.last_seq:
                         self.stale += 1
@@ -89,20 +102,39 @@ class OrderedRepublisher:
                         self.last_seq = seq
                 self.next += 1
 
+    def _release_ordered(self, items: Sequence) -> None:
+        keep = []
+        for seq, item in items:
+            if seq is not None and self.last_seq is not None and seq <= self.last_seq:
+                self.stale += 1
+                continue
+            keep.append(item)
+            if seq is not None:
+                self.last_seq = seq
+        try:
+            out = self.ordered_fn(keep)
+        except BaseException as e:  # keep the stream alive, like a failed batch
+            self.errors.append(e)
+            return
+        for item in out:
+            self.publish_fn(item)
+            self.published += 1
+
 
 class MicroBatchRunner:
     """process_fn(list of messages) → list of (seq, publishable) in message order."""
 
     def __init__(self, process_fn: Callable[[List], List], publish_fn: Callable, batch: int = 8,
-                 capacity: Optional[int] = None, workers: int = 1):
+                 capacity: Optional[int] = None, workers: int = 1,
+                 ordered_fn: Optional[Callable[[List], List]] = None):
         self.batch = max(1, int(batch))
         self.window = LatestWinsWindow(capacity or self.batch * max(1, workers) * 2)
-        self.repub = OrderedRepublisher(publish_fn)
+        self.errors: List[BaseException] = []
+        self.repub = OrderedRepublisher(publish_fn, ordered_fn, self.errors)
         self.process_fn = process_fn
         self._ticket = 0
         self._inflight = 0
         self.batches = 0
-        self.errors: List[BaseException] = []
         self.threads = [threading.Thread(target=self._run, name=f"tca-batch-{i}", daemon=True)
                         for i in range(max(1, workers))]
         for t in self.threads:

@@ -149,6 +149,28 @@ class Detector3D(ABC):
             lab = self._point_labeler = PointLabeler(dev)
         return lab
 
+    def tracker(self, **options):
+        """This engine's :class:`~triton_client_amd.ops.track3d.Tracker3D`, made once (the
+        options of the first call hold) on the engine's GPU when it has one (``label_device`` /
+        ``device``; ``tca_track3d``), else — the ring data-parallel engines among them, where it
+        runs on rank 0's gathered results — with the host definition.  Gates are matched to this
+        engine's class names; the CenterPoint family preloads the paper's nuScenes table, which a
+        ``max_dist`` dict overrides by name and a ``max_dist`` number replaces."""
+        trk = getattr(self, "_tracker", None)
+        if trk is None:
+            from ..ops.track3d import CENTERPOINT_MAX_DIST, Tracker3D
+
+            names = list(getattr(self, "names", None) or [])
+            md = options.pop("max_dist", None)
+            if getattr(self, "family", None) == "centerpoint" and (md is None or isinstance(md, dict)):
+                have = {n.lower() for n in names}
+                md = {**{k: v for k, v in CENTERPOINT_MAX_DIST.items() if k in have},
+                      **{str(k).lower(): v for k, v in (md or {}).items()}}
+            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
+            trk = self._tracker = Tracker3D(max_dist=md, names=names, label_base=getattr(self, "label_base", 1),
+                                            device=dev, **options)
+        return trk
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

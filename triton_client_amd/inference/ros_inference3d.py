@@ -22,6 +22,15 @@ the owner's class, 0 for background; ``instance`` int32: the owner's position in
 the ``boxes`` / ``detections`` array of the box message of the same cloud, -1 for
 none; ``score`` float32, 0 for none).  The owner of a point is the published box
 with the highest score that contains it (``ops/points_in_boxes.py``).
+
+``tracks_topic``: also publish, per cloud and with the cloud's header, a message of
+the box message's type with the same boxes in the same order whose class field
+(``label``, or ``results[0].id``) holds the box's track id instead — the convention
+rviz's jsk display colours by; id 0: not tracked.  The tracker (``ops/track3d.py``:
+greedy closest-centre matching on velocity-compensated positions, ``tca_track3d`` on
+an engine's GPU) sees the clouds in published order: :meth:`RosInference3D.track` is
+the ordered stage of the micro-batched driver, and a cloud the re-publisher drops
+never reaches it.  The box message is the same bytes with the option on or off.
 """
 from __future__ import annotations
 
@@ -45,11 +54,12 @@ def select_boxes(pred: dict, labels: Optional[Sequence[int]] = (2,), score_thres
     return np.nonzero(keep)[0]
 
 
-def jsk_columns(pred: dict, idx) -> dict:
+def jsk_columns(pred: dict, idx, label=None) -> dict:
     """The published fields of the selected boxes as columns (float64 like the
     message): position [n, 3], orientation [n, 4] (yaw about +z, reference
     ``yaw2quaternion`` :117-118), dimensions [n, 3] with the reference's x/y
-    swap (:169-171), value [n] fp32, label [n] uint32."""
+    swap (:169-171), value [n] fp32, label [n] uint32 (``label``: these values instead
+    of the classes, aligned with ``idx``: the tracks message's ids)."""
     idx = np.asarray(idx, np.int64)
     b = np.asarray(pred["pred_boxes"])[idx].astype(np.float64)
     yaw = b[:, 8 if b.shape[-1] >= 9 else 6] if len(b) else np.zeros((0,))
@@ -57,15 +67,15 @@ def jsk_columns(pred: dict, idx) -> dict:
     quat[:, 2], quat[:, 3] = np.sin(yaw / 2), np.cos(yaw / 2)
     return {"position": b[:, :3], "orientation": quat, "dimensions": b[:, [4, 3, 5]] if len(b) else np.zeros((0, 3)),
             "value": np.asarray(pred["pred_scores"])[idx].astype(np.float32),
-            "label": np.asarray(pred["pred_labels"])[idx].astype(np.uint32)}
+            "label": (np.asarray(pred["pred_labels"])[idx] if label is None else np.asarray(label)).astype(np.uint32)}
 
 
-def boxes_to_jsk(pred: dict, idx, header: msgs.Header) -> msgs.BoundingBoxArray:
+def boxes_to_jsk(pred: dict, idx, header: msgs.Header, label=None) -> msgs.BoundingBoxArray:
     """jsk BoundingBoxArray of the selected boxes, built from columns: the
     BoundingBox objects are made only if a subscriber reads ``boxes``
     (:class:`~triton_client_amd.ros.msgs.ArrayList`); serialisation packs the
     columns directly (``ros.rosmsg``)."""
-    cols = jsk_columns(pred, idx)
+    cols = jsk_columns(pred, idx, label)
 
     def build():
         P, Q, D = cols["position"].tolist(), cols["orientation"].tolist(), cols["dimensions"].tolist()
@@ -76,15 +86,17 @@ def boxes_to_jsk(pred: dict, idx, header: msgs.Header) -> msgs.BoundingBoxArray:
     return msgs.BoundingBoxArray(header=header, boxes=msgs.ArrayList(len(cols["value"]), build, cols))
 
 
-def boxes_to_detection3d(pred: dict, idx, header: msgs.Header) -> msgs.Detection3DArray:
+def boxes_to_detection3d(pred: dict, idx, header: msgs.Header, ids=None) -> msgs.Detection3DArray:
+    """``ids``: these values instead of the classes in ``results[0].id``, aligned with ``idx``."""
     arr = msgs.Detection3DArray(header=header)
     b = pred["pred_boxes"]
     yaw_i = 8 if b.shape[-1] >= 9 else 6
-    for i in idx:
+    for k, i in enumerate(idx):
         x = b[i]
         arr.detections.append(msgs.Detection3D(
             header=header,
-            results=[msgs.ObjectHypothesisWithPose(id=int(pred["pred_labels"][i]), score=float(pred["pred_scores"][i]))],
+            results=[msgs.ObjectHypothesisWithPose(id=int(pred["pred_labels"][i] if ids is None else ids[k]),
+                                                   score=float(pred["pred_scores"][i]))],
             bbox=msgs.BoundingBox3D(
                 center=msgs.Pose(msgs.Point(float(x[0]), float(x[1]), float(x[2])),
                                  compat.yaw2quaternion(float(x[yaw_i]))),
@@ -97,7 +109,8 @@ class RosInference3D(BaseInference):
                  bus=None, jsk: bool = True, labels: Optional[Sequence[int]] = (2,), score_thresh: float = 0.5,
                  z_offset: float = 1.5, queue_size: Optional[int] = 50, metrics=None, mode: str = "sync",
                  wire: str = "raw", batch: int = 1, workers: int = 1, bev_topic: Optional[str] = None,
-                 bev_view=None, points_topic: Optional[str] = None):
+                 bev_view=None, points_topic: Optional[str] = None, tracks_topic: Optional[str] = None,
+                 track_options: Optional[dict] = None):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -105,6 +118,8 @@ class RosInference3D(BaseInference):
         if bev_topic:
             self.enable_bev(bev_topic, bev_view)
         self.points_topic, self.points_pub = points_topic or None, None
+        self.tracks_topic, self.tracks_pub = tracks_topic or None, None
+        self.track_options = dict(track_options or {})
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
@@ -123,12 +138,18 @@ class RosInference3D(BaseInference):
             self.bev_pub = compat.Publisher(self.bev_topic, msgs.Image, queue_size=1, bus=self.bus)
         if self.points_topic:
             self.points_pub = compat.Publisher(self.points_topic, msgs.PointCloud2, queue_size=1, bus=self.bus)
+        if self.tracks_topic:
+            self.tracks_pub = compat.Publisher(self.tracks_topic, t, queue_size=1, bus=self.bus)
         cb, qs = self._pc_callback, self.queue_size
         if self.batch > 1 or self.workers > 1:
             from .batching import MicroBatchRunner
-            self.runner = MicroBatchRunner(lambda cs: [self._item(r) for r in self.process(cs)], self._publish,
-                                           batch=self.batch, workers=self.workers,
-                                           capacity=max(self.queue_size or 0, 2 * self.batch * self.workers))
+            cap = max(self.queue_size or 0, 2 * self.batch * self.workers)
+            if self.tracks_topic:  # the workers hand over whole results; the ordered stage tracks them
+                self.runner = MicroBatchRunner(self.process, lambda r: self._publish(self._item(r)), batch=self.batch,
+                                               workers=self.workers, capacity=cap, ordered_fn=self.track)
+            else:
+                self.runner = MicroBatchRunner(lambda cs: [self._item(r) for r in self.process(cs)], self._publish,
+                                               batch=self.batch, workers=self.workers, capacity=cap)
             cb, qs = self.runner.push, None
         self.sub = compat.Subscriber(p["sub_topic"], msgs.PointCloud2, cb, queue_size=qs, bus=self.bus,
                                      ingest=getattr(self.engine, "ingest_buffer", None))
@@ -154,7 +175,8 @@ class RosInference3D(BaseInference):
 
     @staticmethod
     def _item(r: tuple) -> tuple:
-        """What is published of one ``process`` result: (box message, picture or None[, labelled cloud])."""
+        """What is published of one ``process`` (or :meth:`track`) result: (box message, picture or
+        None[, labelled cloud or None[, tracks message]])."""
         return (r[0],) + (tuple(r[2:]) if len(r) > 2 else (None,))
 
     def _publish(self, item) -> None:
@@ -162,8 +184,10 @@ class RosInference3D(BaseInference):
         self.pub.publish(m)
         if im is not None and self.bev_pub is not None:
             self.bev_pub.publish(im)
-        if len(item) > 2 and self.points_pub is not None:
+        if len(item) > 2 and item[2] is not None and self.points_pub is not None:
             self.points_pub.publish(item[2])
+        if len(item) > 3 and self.tracks_pub is not None:
+            self.tracks_pub.publish(item[3])
 
     def to_msg(self, pred: dict, header: msgs.Header):
         idx = select_boxes(pred, self.labels, self.score_thresh)
@@ -219,6 +243,33 @@ class RosInference3D(BaseInference):
         return [(r[0], r[1], r[2] if len(r) > 2 else None, labelled_cloud(c, payload))
                 for r, c, (_, _, payload) in zip(out, clouds, res)]
 
+    def tracker(self):
+        """The engine's tracker, made with ``track_options`` on first use."""
+        fn = getattr(self.engine, "tracker", None)  # (an engine that is no Detector3D subclass)
+        return fn(**self.track_options) if fn is not None else Detector3D.tracker(self.engine, **self.track_options)
+
+    def track(self, results: Sequence[tuple]) -> List[tuple]:
+        """The ordered stage: ``process`` results of consecutive clouds, in published order →
+        each as ``(box message, prediction, picture or None, labelled cloud or None, tracks
+        message)``.  One tracker call per batch; each prediction gains ``track_ids``,
+        ``track_hits`` and ``track_vel``, aligned with the published selection."""
+        results = list(results)
+        if not results:
+            return []
+        timer = StageTimer(self.metrics)
+        with timer("track3d"):
+            preds = [r[1] for r in results]
+            idx = [select_boxes(p, self.labels, self.score_thresh) for p in preds]
+            res = self.tracker().track(preds, idx, [r[0].header.stamp for r in results])
+            out = []
+            for r, p, ix, (ids, hits, vel) in zip(results, preds, idx, res):
+                p["track_ids"], p["track_hits"], p["track_vel"] = ids, hits, vel
+                h = r[0].header
+                m = boxes_to_jsk(p, ix, h, ids) if self.jsk else boxes_to_detection3d(p, ix, h, ids)
+                out.append((r[0], p, r[2] if len(r) > 2 else None, r[3] if len(r) > 3 else None, m))
+        return out
+
     def _pc_callback(self, msg):
-        for r in self.process([msg]):
+        res = self.process([msg])
+        for r in (self.track(res) if self.tracks_topic else res):
             self._publish(self._item(r))
