@@ -93,6 +93,9 @@ def main():
                          "(RosInference compressed=; encoded on the GPU) instead of the raw Image")
     ap.add_argument("--jpeg-quality", type=int, default=90)
     ap.add_argument("--jpeg-subsampling", default="4:2:0", choices=["4:2:0", "4:2:2", "4:4:4"])
+    ap.add_argument("--camera-tracks", action="store_true",
+                    help="camera side: also track the detections and publish them with their track ids "
+                         "(RosInference tracks_topic; the frames are stamped 1/30 s apart)")
     ap.add_argument("--lidar", type=int, default=512, help="PointCloud2 messages (0: skip)")
     ap.add_argument("--bev", action="store_true",
                     help="LiDAR side: also publish the bird's-eye-view Image of every cloud (RosInference3D bev_topic)")
@@ -174,7 +177,8 @@ def main():
             from triton_client_amd.ops.jpeg_encode import JpegOptions
             opts = JpegOptions(quality=a.jpeg_quality, subsampling=a.jpeg_subsampling)
         drv = RosInference(engine=eng2, params={"sub_topic": "/cam", "pub_topic": "/cam_out"}, bus=bus,
-                           batch=a.batch, workers=a.workers, metrics=st, queue_size=window, compressed=opts)
+                           batch=a.batch, workers=a.workers, metrics=st, queue_size=window, compressed=opts,
+                           **({"tracks_topic": "/cam_tracks"} if a.camera_tracks else {}))
         drv.start_inference(spin=False)
         out_type = msgs.CompressedImage if opts is not None else msgs.Image
         _run(bus, "/cam", drv.out_topic, out_type, msgs_in[:warm], window, a.timeout)  # warm-up + graphs
@@ -189,6 +193,13 @@ def main():
                          "output": (f"annotated CompressedImage JPEG q{a.jpeg_quality} {a.jpeg_subsampling}"
                                     if opts is not None else "annotated Image") + " + Detection2DArray",
                          "published_bytes_per_frame": round(sum(sizes) / max(1, len(sizes))), "stages": st.summary()}
+        if a.camera_tracks:
+            trk = drv.tracker()
+            ts = trk.state()
+            out["camera"]["output"] += f" + tracks ({trk.kind})"
+            out["camera"]["tracker"] = trk.kind
+            out["camera"]["tracks"] = {"frames": trk.frames, "ids_given": int(ts.next_id) - 1,
+                                       "live": int((ts.id != 0).sum()), "overflow": int(ts.overflow)}
     if a.lidar:
         spec = LidarSpec(sensor_height=3.23)
         clouds = [compat.create_cloud_xyzi(np.frombuffer(lidar_sweep(spec, s).tobytes(), np.float32).reshape(-1, 4))
@@ -245,24 +256,29 @@ def _camera_input(H, W, encoding):
 
 
 def _camera_messages(H, W, n, encoding=None):
-    """n camera messages over 8 synthetic frames: JPEG CompressedImage, or raw Image in ``encoding``."""
+    """n camera messages over 8 synthetic frames, stamped 1/30 s apart: JPEG CompressedImage, or raw
+    Image in ``encoding``."""
     from PIL import Image
 
     from triton_client_amd.ros import msgs
     from triton_client_amd.utils.synthetic import camera_frame
 
+    def header(i):
+        ns = i * 10 ** 9 // 30
+        return msgs.Header(seq=i + 1, stamp=msgs.Time(100 + ns // 10 ** 9, ns % 10 ** 9), frame_id="cam")
+
     if encoding is not None:
         from triton_client_amd.ops.golden import image_packed_row, rgb8_to_encoding
 
         raws = [rgb8_to_encoding(camera_frame(H, W, s), encoding) for s in range(8)]
-        return [msgs.Image(header=msgs.Header(seq=i + 1, frame_id="cam"), height=H, width=W, encoding=encoding,
+        return [msgs.Image(header=header(i), height=H, width=W, encoding=encoding,
                            is_bigendian=0, step=image_packed_row(W, encoding), data=raws[i % 8]) for i in range(n)]
     jpegs = []
     for s in range(8):
         buf = io.BytesIO()
         Image.fromarray(camera_frame(H, W, s)).save(buf, format="JPEG", quality=90)
         jpegs.append(buf.getvalue())
-    return [msgs.CompressedImage(header=msgs.Header(seq=i + 1, frame_id="cam"), format="jpeg", data=jpegs[i % 8])
+    return [msgs.CompressedImage(header=header(i), format="jpeg", data=jpegs[i % 8])
             for i in range(n)]
 
 

@@ -78,6 +78,9 @@ _KERNEL_SIGS = {
     # rows, det_off (host), F, dt, reset, max_dist2, gates, state, capacity, max_age, alpha, out, stream
     # (csrc/kernels/track3d.hip)
     "tca_track3d": [P, P, I, P, P, P, I, P, I, I, F, P, P],
+    # rows, det_off (host), F, dt, reset, state, capacity, max_age, min_iou, min_iou_low, alpha, beta, out, stream
+    # (csrc/kernels/track2d.hip)
+    "tca_track2d": [P, P, I, P, P, P, I, I, F, F, F, F, P, P],
     "tca_nms_merge": [P, P, P, P, P, P, P, P, I, I, I, F, I, I, P, P, P, P, P, P],
     "tca_pc2_unpack": [P, P, P, I, I, I, P, P, I, F, P, I, P, P, P, P],
     "tca_pc2_blocks_per_frame": [I],

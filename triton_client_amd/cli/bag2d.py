@@ -5,7 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import DATA, add_framework_flags, add_reference_flags, jpeg_options, load_params, setup_logging
+from .common import (DATA, add_framework_flags, add_reference_flags, add_track2d_flags, jpeg_options, load_params,
+                     setup_logging, track2d_options)
 from .engines import engine_2d, export_if_asked, maybe_data_parallel
 
 
@@ -18,6 +19,8 @@ def parse_args(argv=None):
     p.add_argument("--out-bag", default=None, help="write input + annotated image + detections here")
     p.add_argument("--start-seq", type=int, default=0, help="resume after this many frames")
     p.add_argument("--max-frames", type=int, default=None)
+    add_track2d_flags(p, "track the detections in bag order and, with --out-bag, write them with their track ids in "
+                         "place of their classes to the output bag on this topic")
     return p.parse_args(argv)
 
 
@@ -41,7 +44,8 @@ def main(argv=None) -> int:
             return 0
     drv = BagInference2D(channel, client, engine=engine, params=params, bagfile=flags.bag, out_dir=flags.out or None,
                          out_bag=flags.out_bag, batch=max(1, flags.frames_per_step), save_png=bool(flags.out),
-                         start_seq=flags.start_seq, max_frames=flags.max_frames, compressed=jpeg_options(flags))
+                         start_seq=flags.start_seq, max_frames=flags.max_frames, compressed=jpeg_options(flags),
+                         tracks_topic=flags.tracks_topic or None, track_options=track2d_options(flags))
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

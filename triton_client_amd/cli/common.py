@@ -179,6 +179,23 @@ def track_options(flags) -> dict:
     return opts
 
 
+def add_track2d_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--tracks-topic, --track-max-age, --track-high-score, --track-min-iou (``ops/track2d.py``)."""
+    p.add_argument("--tracks-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--track-max-age", type=int, default=30, metavar="FRAMES",
+                   help="a track missed this many frames in a row still comes back with its id")
+    p.add_argument("--track-high-score", type=float, default=0.5, metavar="SCORE",
+                   help="detections scoring at least this may match any live track; lower ones only keep alive a "
+                        "track matched in the previous frame")
+    p.add_argument("--track-min-iou", type=float, default=0.2, metavar="IOU",
+                   help="association gate of the high-score detections: IoU with the track's predicted box")
+
+
+def track2d_options(flags) -> dict:
+    """The ``track_options`` of the 2D --track-* flags."""
+    return {"max_age": flags.track_max_age, "high_score": flags.track_high_score, "min_iou": flags.track_min_iou}
+
+
 def bev_view(engine, res: float, enabled):
     """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
     range for an engine that does not know its model's) at ``res`` metres per pixel; None

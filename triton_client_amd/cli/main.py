@@ -5,8 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_framework_flags, add_reference_flags, image_files, jpeg_options, load_params,
-                     play_bag, setup_logging)
+from .common import (DATA, add_framework_flags, add_reference_flags, add_track2d_flags, image_files, jpeg_options,
+                     load_params, play_bag, setup_logging, track2d_options)
 from .engines import engine_2d, export_if_asked, maybe_data_parallel
 
 
@@ -14,6 +14,8 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__)
     add_reference_flags(p, "YOLOv5n")
     add_framework_flags(p, os.path.join(DATA, "client_parameter.yaml"))
+    add_track2d_flags(p, "also publish the detections of every frame here with their track ids in place of their "
+                         "classes (a Detection2DArray)")
     return p.parse_args(argv)
 
 
@@ -44,7 +46,8 @@ def main(argv=None) -> int:
     bus = default_bus() if (flags.play or flags.image_src == "local" or not compat.HAVE_ROSPY) else None
     drv = RosInference(channel, client, engine=engine, params=params, bus=bus, metrics=metrics,
                        queue_size=None if flags.play or flags.image_src == "local" else 1,
-                       batch=flags.live_batch, workers=flags.live_workers, compressed=jpeg_options(flags))
+                       batch=flags.live_batch, workers=flags.live_workers, compressed=jpeg_options(flags),
+                       tracks_topic=flags.tracks_topic or None, track_options=track2d_options(flags))
     if flags.image_src == "local":
         rc = _run_local_images(drv, flags, params)
         export_if_asked(flags, engine)

@@ -7,7 +7,8 @@ window of remote RPCs per micro-batch) instead of one blocking RPC per frame.
 2D: annotated PNGs to ``out_dir/NNNN.png`` and, if ``out_bag`` is given, the
 input image + annotated image + Detection2DArray written to it (the
 reference opened ``output.bag`` but never wrote); with ``compressed=`` the annotated
-image is a JPEG ``CompressedImage`` on ``<pub_topic>/compressed``.  3D: the input cloud and
+image is a JPEG ``CompressedImage`` on ``<pub_topic>/compressed``; with ``tracks_topic=`` the
+frames are tracked in bag order and the tracks message is written to that topic.  3D: the input cloud and
 the BoundingBoxArray are written to ``<bag>_output.bag`` like the
 reference.  Bag path and output dir are arguments (fixes A14);
 ``start_seq`` resumes a replay.
@@ -63,6 +64,7 @@ class BagInference2D(RosInference):
         self.bagfile, self.out_dir, self.out_bag = bagfile, out_dir, out_bag
         self.batch, self.save_png, self.start_seq, self.max_frames = batch, save_png, start_seq, max_frames
         self.results = []
+        self.tracks = []  # with tracks_topic: (seq, (track_id, hits, vel)) per frame
         self.elapsed = 0.0
 
     def start_inference(self, spin: bool = False, timeout: Optional[float] = None):
@@ -80,14 +82,21 @@ class BagInference2D(RosInference):
                     chunk = chunk[: max(0, self.max_frames - count)]
                     if not chunk:
                         break
-                for m, (im, det, d) in zip(chunk, self.process(chunk)):
+                res = self.process(chunk)
+                if self.tracks_topic:  # the frames are tracked in bag order
+                    res = self.track(res)
+                for m, (im, det, d, *trk) in zip(chunk, res):
                     if self.save_png and self.out_dir:
                         _save_png(os.path.join(self.out_dir, f"{count:04}.png"), im)
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
                         ob.write(self.out_topic, im)  # <pub_topic>, or <pub_topic>/compressed (JPEG)
                         ob.write(p["pub_topic"] + "/detections", det)
+                        if trk:
+                            ob.write(self.tracks_topic, trk[0])
                     self.results.append((m.header.seq, d))
+                    if trk:
+                        self.tracks.append((m.header.seq, trk[1]))
                     count += 1
         self.elapsed = time.perf_counter() - t0
         if ob is not None:

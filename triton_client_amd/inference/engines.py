@@ -90,6 +90,18 @@ class Detector2D(ABC):
     def detect(self, frames: Sequence[np.ndarray]) -> List[np.ndarray]:
         """frames: HxWx3 uint8 RGB arrays → per-frame [n, 6] detections."""
 
+    def tracker(self, **options):
+        """This engine's :class:`~triton_client_amd.ops.track2d.Tracker2D`, made once (the
+        options of the first call hold) on the engine's GPU when it has one (``device``;
+        ``tca_track2d``), else — the ring data-parallel engines among them, where it runs on
+        rank 0's gathered results — with the host definition."""
+        trk = getattr(self, "_tracker", None)
+        if trk is None:
+            from ..ops.track2d import Tracker2D
+
+            trk = self._tracker = Tracker2D(device=getattr(self, "device", None) or "cpu", **options)
+        return trk
+
 
 class Detector3D(ABC):
     names: List[str] = []

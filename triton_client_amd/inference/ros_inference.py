@@ -17,6 +17,17 @@ re-published in ``header.seq`` order (:mod:`.batching`).
 ``Image`` -- about a thirteenth of the bytes.  The local GPU engine encodes on the
 device inside its captured step (``ops/jpeg_encode.py``); every other engine encodes
 the annotated array with PIL on the host.  The data-parallel ring engines refuse it.
+
+``tracks_topic``: also publish, per frame and with the frame's header, one more
+``Detection2DArray`` with the same detections in the same order whose ``results[0].id``
+holds the detection's track id instead of its class (the convention of the 3D tracks
+message; id 0: not tracked).  The tracker (``ops/track2d.py``: ByteTrack's association
+on the IoU of predicted boxes, ``tca_track2d`` on an engine's GPU) sees the frames in
+published order: :meth:`RosInference.track` is the ordered stage of the micro-batched
+driver, and a frame the re-publisher drops never reaches it.  The annotated frame and
+the detections message are the same bytes with the option on or off; track ids are
+not drawn on the frame (the drawing happens in the engine's step, before the ordered
+stage).
 """
 from __future__ import annotations
 
@@ -40,30 +51,37 @@ def decode_image_msg(msg) -> np.ndarray:
     return compat.imgmsg_to_numpy(msg, "rgb8")
 
 
-def detections_to_msg(dets: np.ndarray, header: msgs.Header, source: Optional[msgs.Image] = None) -> msgs.Detection2DArray:
+def detections_to_msg(dets: np.ndarray, header: msgs.Header, source: Optional[msgs.Image] = None,
+                      ids=None) -> msgs.Detection2DArray:
     """Detection2DArray over dets [n, 6]; the Detection2D objects are built only
     if a subscriber reads ``detections`` (:class:`~triton_client_amd.ros.msgs.ArrayList`,
-    columns ``{"dets": dets}``)."""
+    columns ``{"dets": dets}``).  ``ids`` [n]: these values instead of the classes in
+    ``results[0].id`` (the tracks message's ids; one more column ``"ids"``)."""
     dets = np.asarray(dets, np.float32).reshape(-1, 6)
+    cols = {"dets": dets}
+    if ids is not None:
+        cols["ids"] = ids = np.asarray(ids, np.int32).reshape(-1)
 
     def build():
         src = msgs.Image(header=header) if source is None else source
         out = []
-        for x1, y1, x2, y2, conf, c in dets.tolist():
+        for k, (x1, y1, x2, y2, conf, c) in enumerate(dets.tolist()):
             out.append(msgs.Detection2D(
-                header=header, results=[msgs.ObjectHypothesisWithPose(id=int(c), score=conf)],
+                header=header, results=[msgs.ObjectHypothesisWithPose(id=int(c if ids is None else ids[k]),
+                                                                      score=conf)],
                 bbox=msgs.BoundingBox2D(center=msgs.Pose2D((x1 + x2) / 2, (y1 + y2) / 2, 0.0), size_x=x2 - x1,
                                         size_y=y2 - y1),
                 source_img=src))
         return out
-    return msgs.Detection2DArray(header=header, detections=msgs.ArrayList(len(dets), build, {"dets": dets}))
+    return msgs.Detection2DArray(header=header, detections=msgs.ArrayList(len(dets), build, cols))
 
 
 class RosInference(BaseInference):
     def __init__(self, channel=None, client=None, engine: Optional[Detector2D] = None, params: Optional[dict] = None,
                  bus=None, letterbox: bool = False, conf_thres: float = 0.3, draw: bool = True,
                  publish_detections: bool = True, queue_size: Optional[int] = 1, metrics=None, mode: str = "sync",
-                 wire: str = "raw", batch: int = 1, workers: int = 1, compressed=None):
+                 wire: str = "raw", batch: int = 1, workers: int = 1, compressed=None,
+                 tracks_topic: Optional[str] = None, track_options: Optional[dict] = None):
         super().__init__(channel, client)
         if compressed is not None and not getattr(engine, "compressed_out", True):
             raise ValueError(f"{type(engine).__name__} does not publish compressed frames: the data-parallel ring "
@@ -77,6 +95,8 @@ class RosInference(BaseInference):
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
         self.sub = self.pub = self.det_pub = None
+        self.tracks_topic, self.tracks_pub = tracks_topic or None, None
+        self.track_options = dict(track_options or {})
         self.batch, self.workers = max(1, batch), max(1, workers)
         self.runner = None
 
@@ -91,12 +111,19 @@ class RosInference(BaseInference):
         if self.publish_detections:
             self.det_pub = compat.Publisher(p["pub_topic"] + "/detections", msgs.Detection2DArray, queue_size=10,
                                             bus=self.bus)
+        if self.tracks_topic:
+            self.tracks_pub = compat.Publisher(self.tracks_topic, msgs.Detection2DArray, queue_size=10, bus=self.bus)
         cb, qs = self._callback, self.queue_size
         if self.batch > 1 or self.workers > 1:
             from .batching import MicroBatchRunner
-            self.runner = MicroBatchRunner(lambda ms: [(im, det) for im, det, _ in self.process(ms)], self._publish,
-                                           batch=self.batch, workers=self.workers,
-                                           capacity=max(self.queue_size or 0, 2 * self.batch * self.workers))
+            cap = max(self.queue_size or 0, 2 * self.batch * self.workers)
+            if self.tracks_topic:  # the workers hand over whole results; the ordered stage tracks them
+                self.runner = MicroBatchRunner(self.process, lambda r: self._publish((r[0], r[1], r[3])),
+                                               batch=self.batch, workers=self.workers, capacity=cap,
+                                               ordered_fn=self.track)
+            else:
+                self.runner = MicroBatchRunner(lambda ms: [(im, det) for im, det, _ in self.process(ms)],
+                                               self._publish, batch=self.batch, workers=self.workers, capacity=cap)
             cb, qs = self.runner.push, None  # the window is the (latest-wins) queue
         self.sub = compat.Subscriber(p["sub_topic"], msgs.CompressedImage, cb, queue_size=qs, bus=self.bus,
                                      ingest=getattr(self.engine, "ingest_buffer", None))
@@ -112,10 +139,13 @@ class RosInference(BaseInference):
             self.runner = None
 
     def _publish(self, item) -> None:
-        im, det = item
+        """item: (frame, detections message[, tracks message])."""
+        im, det = item[0], item[1]
         self.pub.publish(im)
         if self.det_pub is not None:
             self.det_pub.publish(det)
+        if len(item) > 2 and self.tracks_pub is not None:
+            self.tracks_pub.publish(item[2])
 
     # ------------------------------------------------------------------ work
     def _live(self):
@@ -184,8 +214,30 @@ class RosInference(BaseInference):
             self.metrics.frame(len(images))
         return out
 
+    def tracker(self):
+        """The engine's tracker, made with ``track_options`` on first use."""
+        fn = getattr(self.engine, "tracker", None)  # (an engine that is no Detector2D subclass)
+        return fn(**self.track_options) if fn is not None else Detector2D.tracker(self.engine, **self.track_options)
+
+    def track(self, results: Sequence[tuple]) -> List[tuple]:
+        """The ordered stage: ``process`` results of consecutive frames, in published order →
+        each as ``(frame, detections message, dets [n, 6], tracks message, (track_id [n], hits
+        [n], vel [n, 2]))``, aligned with the frame's detections.  One tracker call per batch."""
+        results = list(results)
+        if not results:
+            return []
+        timer = StageTimer(self.metrics)
+        with timer("track2d"):
+            res = self.tracker().track([r[2] for r in results], [r[1].header.stamp for r in results])
+            return [(r[0], r[1], r[2], detections_to_msg(r[2], r[1].header, ids=t[0]), t) for r, t in zip(results, res)]
+
     def _callback(self, msg):
-        for im, det, _ in self.process([msg]):
+        res = self.process([msg])
+        if self.tracks_topic:
+            for r in self.track(res):
+                self._publish((r[0], r[1], r[3]))
+            return
+        for im, det, _ in res:
             self.pub.publish(im)
             if self.det_pub is not None:
                 self.det_pub.publish(det)
