@@ -56,8 +56,9 @@ class _Stages:
         return {k: {"calls": self.n[k], "ms_per_call": round(1e3 * v / self.n[k], 3)} for k, v in self.sum.items()}
 
 
-def _run(bus, pub_topic, out_topic, out_type, messages, window, timeout, published=None):
-    """published: a list that receives the payload bytes of every output message."""
+def _run(bus, pub_topic, out_topic, out_type, messages, window, timeout, published=None, side=None):
+    """published: a list that receives the payload bytes of every output message.  side: (topic,
+    messages) published one by one, each just before the input message of the same index."""
     from triton_client_amd.ros import compat
 
     got = []
@@ -71,10 +72,13 @@ def _run(bus, pub_topic, out_topic, out_type, messages, window, timeout, publish
             done.set()
     sub = compat.Subscriber(out_topic, out_type, on_out, bus=bus)
     pub = compat.Publisher(pub_topic, type(messages[0]), bus=bus)
+    side_pub = compat.Publisher(side[0], type(side[1][0]), bus=bus) if side else None
     t0 = time.perf_counter()
     for i, m in enumerate(messages):
         while i - len(got) >= window:  # pace: never more than `window` messages in flight
             time.sleep(0.0002)
+        if side_pub is not None:
+            side_pub.publish(side[1][i])
         pub.publish(m)
     ok = done.wait(timeout)
     t1 = time.perf_counter()
@@ -104,6 +108,9 @@ def main():
     ap.add_argument("--tracks", action="store_true",
                     help="LiDAR side: also track the detections and publish the boxes with their track ids "
                          "(RosInference3D tracks_topic; the clouds are stamped 0.1 s apart)")
+    ap.add_argument("--ranged", action="store_true",
+                    help="LiDAR side: also range 64 synthetic camera detections per cloud, stamped like the cloud, "
+                         "under a fixed KITTI-like calibration (RosInference3D ranged_topic)")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -218,12 +225,22 @@ def main():
                              batch=a.batch, workers=a.workers, metrics=st, queue_size=window,
                              bev_topic="/pc_bev" if a.bev else None,
                              **({"points_topic": "/pc_points"} if a.points else {}),
-                             **({"tracks_topic": "/pc_tracks"} if a.tracks else {}))
+                             **({"tracks_topic": "/pc_tracks"} if a.tracks else {}),
+                             **({"ranged_topic": "/cam_ranged", "camera_detections_topic": "/cam_det",
+                                 "calibration": _kitti_like_calibration()} if a.ranged else {}))
+        dets = _detection_messages(msgs_in) if a.ranged else None
+        ranged = []
+        rsub = compat.Subscriber("/cam_ranged", msgs.Detection2DArray, ranged.append, bus=bus) if a.ranged else None
         drv.start_inference(spin=False)
-        _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout)
+        _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout,
+             side=("/cam_det", dets[:warm]) if dets else None)
         st.sum.clear(), st.n.clear()
-        n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout)
+        del ranged[:]
+        n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout,
+                         side=("/cam_det", dets[warm:]) if dets else None)
         drv.stop()
+        if rsub is not None:
+            rsub.unregister()
         if info is not None:
             eng3.close()
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
@@ -237,6 +254,15 @@ def main():
             out["lidar"]["bev_painter"] = painter
         if a.points:
             out["lidar"]["output"] += " + labelled PointCloud2 (28 B per point)"
+        if a.ranged:
+            from triton_client_amd.inference.engines import Detector3D
+            from triton_client_amd.ops.range2d import device_enabled
+            kind = "tca_range2d" if Detector3D.ranger(eng3).gpu and device_enabled() else "host definition"
+            got = sum(1 for m in ranged for d in m.detections if d.results[0].pose.position.z != 0.0)
+            out["lidar"]["output"] += f" + ranged Detection2DArray ({kind})"
+            out["lidar"]["ranger"] = kind
+            out["lidar"]["ranged"] = {"messages": len(ranged), "detections": sum(len(m.detections) for m in ranged),
+                                      "with_range": got}
         if a.tracks:
             trk = drv.tracker()
             ts = trk.state()
@@ -280,6 +306,33 @@ def _camera_messages(H, W, n, encoding=None):
         jpegs.append(buf.getvalue())
     return [msgs.CompressedImage(header=header(i), format="jpeg", data=jpegs[i % 8])
             for i in range(n)]
+
+
+def _kitti_like_calibration():
+    """A fixed rig: KITTI's colour-camera projection, the LiDAR looking along the camera's axis
+    from 8 cm above and 27 cm behind it."""
+    from triton_client_amd.ops.range2d import Calibration
+
+    P = [[721.5377, 0.0, 609.5593, 44.85728], [0.0, 721.5377, 172.854, 0.2163791], [0.0, 0.0, 1.0, 0.002745884]]
+    T = [[0.0, -1.0, 0.0, 0.0], [0.0, 0.0, -1.0, -0.08], [1.0, 0.0, 0.0, -0.27], [0.0, 0.0, 0.0, 1.0]]
+    return Calibration(np.array(P), np.array(T))
+
+
+def _detection_messages(clouds, per_cloud=64):
+    """One Detection2DArray per cloud, stamped like it: ``per_cloud`` seeded boxes on a 1242 x 375 image."""
+    from triton_client_amd.ros import msgs
+
+    out = []
+    for i, c in enumerate(clouds):
+        rng = np.random.default_rng(i % 8)
+        box = np.stack([rng.uniform(0, 1242, per_cloud), rng.uniform(120, 375, per_cloud),
+                        rng.uniform(20, 300, per_cloud), rng.uniform(20, 200, per_cloud)], 1)
+        dets = [msgs.Detection2D(results=[msgs.ObjectHypothesisWithPose(id=1 + k % 3, score=0.9)],
+                                 bbox=msgs.BoundingBox2D(msgs.Pose2D(float(b[0]), float(b[1])), float(b[2]), float(b[3])))
+                for k, b in enumerate(box)]
+        out.append(msgs.Detection2DArray(header=msgs.Header(seq=c.header.seq, stamp=c.header.stamp, frame_id="cam"),
+                                         detections=dets))
+    return out
 
 
 def _cloud_messages(n):

@@ -81,6 +81,10 @@ _KERNEL_SIGS = {
     # rows, det_off (host), F, dt, reset, state, capacity, max_age, min_iou, min_iou_low, alpha, beta, out, stream
     # (csrc/kernels/track2d.hip)
     "tca_track2d": [P, P, I, P, P, P, I, I, F, F, F, F, P, P],
+    # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z, box_off (host), table, M (host), bin_w,
+    # min_depth, pct, min_points, window, hist, out, stream (csrc/kernels/range2d.hip)
+    "tca_range2d": [P, L, P, P, I, I, I, I, I, I, P, P, P, F, F, I, I, I, P, P, P],
+    "tca_range2d_bins": [],  # returns the depth bins per box (not an error code)
     "tca_nms_merge": [P, P, P, P, P, P, P, P, I, I, I, F, I, I, P, P, P, P, P, P],
     "tca_pc2_unpack": [P, P, P, I, I, I, P, P, I, F, P, I, P, P, P, P],
     "tca_pc2_blocks_per_frame": [I],

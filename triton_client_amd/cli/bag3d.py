@@ -5,8 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_framework_flags, add_reference_flags, add_track_flags, bev_view, labels_arg,
-                     load_params, setup_logging, track_options)
+from .common import (DATA, add_framework_flags, add_range_flags, add_reference_flags, add_track_flags, bev_view,
+                     labels_arg, load_params, range_options, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -26,7 +26,12 @@ def parse_args(argv=None):
                         "the output bag on this topic")
     add_track_flags(p, "write the boxes of every cloud, with their track ids in place of their classes, to the "
                        "output bag on this topic")
-    return p.parse_args(argv)
+    add_range_flags(p, "write, per cloud, the nearest camera Detection2DArray of --camera-detections-topic (read from "
+                       "the bag in a first pass) to the output bag on this topic, with each detection's "
+                       "camera-frame position from the LiDAR points (needs --calib)")
+    flags = p.parse_args(argv)
+    flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
+    return flags
 
 
 def main(argv=None) -> int:
@@ -51,7 +56,10 @@ def main(argv=None) -> int:
                          labels=labels_arg(flags.labels), score_thresh=flags.score_thresh,
                          bev_out=flags.bev_out or None, bev_view=bev_view(engine, flags.bev_res, flags.bev_out),
                          points_topic=flags.points_topic or None, tracks_topic=flags.tracks_topic or None,
-                         track_options=track_options(flags))
+                         track_options=track_options(flags), ranged_topic=flags.ranged_topic or None,
+                         camera_detections_topic=flags.camera_detections_topic or None,
+                         calibration=flags.calibration, range_options=flags.range_options,
+                         range_slop=flags.range_slop)
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

@@ -196,6 +196,56 @@ def track2d_options(flags) -> dict:
     return {"max_age": flags.track_max_age, "high_score": flags.track_high_score, "min_iou": flags.track_min_iou}
 
 
+def add_range_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--ranged-topic, --camera-detections-topic, --calib and --range-* (``ops/range2d.py``)."""
+    p.add_argument("--ranged-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--camera-detections-topic", default="", metavar="TOPIC",
+                   help="the camera's vision_msgs/Detection2DArray topic that --ranged-topic ranges")
+    p.add_argument("--calib", default="", metavar="FILE",
+                   help="camera-LiDAR calibration: YAML with projection (3x3 or 3x4) and lidar_to_camera (3x4 or "
+                        "4x4), or a KITTI calib/*.txt (P2, R0_rect, Tr_velo_to_cam)")
+    p.add_argument("--range-slop", type=float, default=0.05, metavar="S",
+                   help="a cloud pairs with the camera message nearest in time within this many seconds")
+    p.add_argument("--range-shrink", type=float, default=0.6, metavar="F",
+                   help="the pixel box is shrunk about its centre by this factor, in (0, 1], before points count")
+    p.add_argument("--range-quantile", type=int, default=50, metavar="PCT",
+                   help="the depth quantile that picks the object's depth bin, 1..100")
+    p.add_argument("--range-min-points", type=int, default=3, metavar="N",
+                   help="a box with fewer points inside gets no range")
+    p.add_argument("--range-bin", type=float, default=0.25, metavar="M",
+                   help="depth bin width in metres (512 bins: 0.25 reaches 128 m)")
+
+
+def range_options(flags, error=None):
+    """``(calibration, range_options)`` of the --calib / --range-* flags, ``(None, {})`` without
+    --ranged-topic.  A ranged topic without a calibration or a detections topic, a calibration
+    that does not load and an option out of range are usage errors: ``error`` (an
+    ``ArgumentParser.error``) is called with the message, else ``ValueError`` is raised."""
+    if not getattr(flags, "ranged_topic", ""):
+        return None, {}
+    from ..ops.range2d import RangeOptions, load_calibration
+
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    if not flags.calib:
+        fail("--ranged-topic needs --calib FILE")
+    if not flags.camera_detections_topic:
+        fail("--ranged-topic needs --camera-detections-topic TOPIC")
+    if not (flags.range_slop >= 0):
+        fail("--range-slop must be >= 0")
+    opts = {"shrink": flags.range_shrink, "pct": flags.range_quantile, "min_points": flags.range_min_points,
+            "bin_w": flags.range_bin}
+    try:
+        RangeOptions(**opts)
+        cal = load_calibration(flags.calib)
+    except (ValueError, OSError) as e:
+        fail(f"--ranged-topic: {e}")
+    return cal, opts
+
+
 def bev_view(engine, res: float, enabled):
     """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
     range for an engine that does not know its model's) at ``res`` metres per pixel; None

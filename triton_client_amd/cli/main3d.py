@@ -5,8 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_framework_flags, add_reference_flags, add_track_flags, bev_view, labels_arg,
-                     load_params, play_bag, setup_logging, track_options)
+from .common import (DATA, add_framework_flags, add_range_flags, add_reference_flags, add_track_flags, bev_view,
+                     labels_arg, load_params, play_bag, range_options, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -21,7 +21,11 @@ def parse_args(argv=None):
                    help="also publish every cloud with its labels here: a PointCloud2 of x, y, z, intensity, label, "
                         "instance (index into the box message), score per point")
     add_track_flags(p, "also publish the boxes of every cloud here with their track ids in place of their classes")
-    return p.parse_args(argv)
+    add_range_flags(p, "also publish, per cloud, the nearest camera Detection2DArray of --camera-detections-topic here "
+                       "with each detection's camera-frame position from the LiDAR points (needs --calib)")
+    flags = p.parse_args(argv)
+    flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
+    return flags
 
 
 def main(argv=None) -> int:
@@ -48,9 +52,13 @@ def main(argv=None) -> int:
                          batch=flags.live_batch, workers=flags.live_workers, bev_topic=flags.bev_topic or None,
                          bev_view=bev_view(engine, flags.bev_res, flags.bev_topic),
                          points_topic=flags.points_topic or None, tracks_topic=flags.tracks_topic or None,
-                         track_options=track_options(flags))
+                         track_options=track_options(flags), ranged_topic=flags.ranged_topic or None,
+                         camera_detections_topic=flags.camera_detections_topic or None,
+                         calibration=flags.calibration, range_options=flags.range_options,
+                         range_slop=flags.range_slop)
     if flags.play:
-        play_bag(flags.play, bus, topics=[params["sub_topic"]])
+        play_bag(flags.play, bus, topics=[params["sub_topic"]] + ([flags.camera_detections_topic]
+                                                                  if flags.ranged_topic else []))
     drv.start_inference(spin=True, timeout=flags.spin_timeout)
     drv.stop()
     if hasattr(engine, "release_transport"):  # a remote client's shared-memory regions

@@ -120,7 +120,10 @@ class BagInference3D(RosInference3D):
         ``NNNN.png`` (the naming of the 2D replay's ``out_dir``) and, with an output bag,
         written to it on ``bev_topic`` (default ``<pub_topic>/bev``).  With ``points_topic`` the
         labelled cloud of every input cloud is written to the output bag on that topic, and with
-        ``tracks_topic`` the tracks message (the clouds are tracked in bag order)."""
+        ``tracks_topic`` the tracks message (the clouds are tracked in bag order).  With
+        ``ranged_topic`` the bag's ``camera_detections_topic`` is read in a first pass, so the
+        pairing is deterministic, and the ranged message of every cloud that has a partner is
+        written on that topic."""
         super().__init__(channel, client, **kw)
         self.bev_out = bev_out or None
         if self.bev_out and not self.bev_topic:
@@ -138,6 +141,14 @@ class BagInference3D(RosInference3D):
         ob = Bag(self.out_bag, "w") if self.out_bag else None
         count = 0
         t0 = time.perf_counter()
+        if self.ranged_topic:  # a first pass holds every camera message: replay misses no partner
+            from ..ops.range2d import StampPairer
+
+            with Bag(self.bagfile) as bag:
+                held = [m for _, m, _ in bag.read_messages(topics=[self.camera_detections_topic])]
+            self.pairer = StampPairer(capacity=max(1, len(held)))
+            for m in held:
+                self.pairer.push(m)
         with Bag(self.bagfile) as bag:
             it = (m for _, m, _ in bag.read_messages(topics=[p["sub_topic"]], start_seq=self.start_seq,
                                                      **_read_kw(self.engine)))
@@ -162,6 +173,8 @@ class BagInference3D(RosInference3D):
                             ob.write(self.points_topic, pic[1])
                         if len(pic) > 2:
                             ob.write(self.tracks_topic, pic[2])
+                        if self.ranged_topic and pred.get("ranged") is not None:
+                            ob.write(self.ranged_topic, pred["ranged"])
                     if self.verbose:
                         print(m.header.seq)
                     self.results.append((m.header.seq, pred))

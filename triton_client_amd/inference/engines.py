@@ -183,6 +183,40 @@ class Detector3D(ABC):
                                             device=dev, **options)
         return trk
 
+    def ranger(self):
+        """This engine's :class:`~triton_client_amd.ops.range2d.CameraRanger`, made once: on the
+        engine's GPU when it has one (``label_device`` / ``device``; ``tca_range2d``), else — the
+        ring data-parallel engines among them — with the host definition."""
+        rng = getattr(self, "_ranger", None)
+        if rng is None:
+            from ..ops.range2d import CameraRanger
+
+            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
+            rng = self._ranger = CameraRanger(dev)
+        return rng
+
+    def range_detections(self, clouds: Sequence[msgs.PointCloud2], detection_msgs: Sequence, calibration,
+                         **options) -> List[Optional[msgs.Detection2DArray]]:
+        """How far away each camera detection is: per cloud, its partner ``detection_msgs[b]`` (a
+        ``Detection2DArray``; None: no partner, the result is None) with
+        ``results[0].pose.position`` set to the camera-frame position of the LiDAR points its
+        shrunken box sees (``ops.range2d``; zero without a range).  ``options``: the fields of
+        :class:`~triton_client_amd.ops.range2d.RangeOptions`.  Points are the message's own x, y,
+        z: ``calibration.T`` starts in the sensor frame."""
+        from ..ops import range2d as r2
+
+        opts = r2.RangeOptions(**options)
+        idx = [b for b, d in enumerate(detection_msgs) if d is not None]
+        out: List[Optional[msgs.Detection2DArray]] = [None] * len(clouds)
+        if not idx:
+            return out
+        rows = [r2.box_rows(r2.bbox_array(detection_msgs[b]), opts.shrink) for b in idx]
+        res = Detector3D.ranger(self).range([clouds[b] for b in idx], rows, calibration.M, opts)  # (duck-typed too)
+        for b, (_, m, c, sums) in zip(idx, res):
+            ok, _, cam = r2.finish(m, c, sums, calibration.T)
+            out[b] = r2.ranged_message(detection_msgs[b], cam, ok)
+        return out
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

@@ -31,6 +31,20 @@ greedy closest-centre matching on velocity-compensated positions, ``tca_track3d`
 an engine's GPU) sees the clouds in published order: :meth:`RosInference3D.track` is
 the ordered stage of the micro-batched driver, and a cloud the re-publisher drops
 never reaches it.  The box message is the same bytes with the option on or off.
+
+``ranged_topic`` (with ``camera_detections_topic`` and ``calibration``): the driver also
+subscribes a camera's ``Detection2DArray`` topic into a ``StampPairer`` and, per batch,
+pairs every cloud with the held camera message nearest in time within ``range_slop``
+seconds (default 0.05) and ranges them in one call (``ops/range2d.py``: ``tca_range2d``
+on an engine's GPU).  A cloud that found a partner publishes one ``Detection2DArray``
+with the camera message's header and its detections in order, bbox and hypotheses kept,
+``results[0].pose.position`` the camera-frame position of the points the shrunken box
+sees; a detection without a range keeps a zero position (``z = 0`` is no ranged value:
+only points at least ``min_depth`` ahead count), one without a hypothesis gets one with
+id 0 and score 0.  Live pairing is best effort: a camera message that arrives after its
+cloud was processed is missed (bag replay reads the camera topic first and misses none).
+The message rides in the prediction as ``pred["ranged"]``; every other message keeps its
+bytes, and with the option off nothing changes.
 """
 from __future__ import annotations
 
@@ -110,7 +124,9 @@ class RosInference3D(BaseInference):
                  z_offset: float = 1.5, queue_size: Optional[int] = 50, metrics=None, mode: str = "sync",
                  wire: str = "raw", batch: int = 1, workers: int = 1, bev_topic: Optional[str] = None,
                  bev_view=None, points_topic: Optional[str] = None, tracks_topic: Optional[str] = None,
-                 track_options: Optional[dict] = None):
+                 track_options: Optional[dict] = None, ranged_topic: Optional[str] = None,
+                 camera_detections_topic: Optional[str] = None, calibration=None,
+                 range_options: Optional[dict] = None, range_slop: float = 0.05):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -120,6 +136,18 @@ class RosInference3D(BaseInference):
         self.points_topic, self.points_pub = points_topic or None, None
         self.tracks_topic, self.tracks_pub = tracks_topic or None, None
         self.track_options = dict(track_options or {})
+        self.ranged_topic, self.ranged_pub, self.camera_sub = ranged_topic or None, None, None
+        self.camera_detections_topic, self.calibration = camera_detections_topic or None, calibration
+        self.range_options, self.range_slop = dict(range_options or {}), float(range_slop)
+        self.pairer = None
+        if self.ranged_topic:
+            from ..ops.range2d import RangeOptions, StampPairer
+
+            if calibration is None or not self.camera_detections_topic:
+                raise ValueError("ranged_topic needs calibration and camera_detections_topic")
+            RangeOptions(**self.range_options)  # a bad option fails here, not in the first batch
+            # holds a camera message for as long as its cloud may wait in the driver's window
+            self.pairer = StampPairer(max(64, queue_size or 0, 2 * max(1, batch) * max(1, workers)))
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
@@ -140,6 +168,10 @@ class RosInference3D(BaseInference):
             self.points_pub = compat.Publisher(self.points_topic, msgs.PointCloud2, queue_size=1, bus=self.bus)
         if self.tracks_topic:
             self.tracks_pub = compat.Publisher(self.tracks_topic, t, queue_size=1, bus=self.bus)
+        if self.ranged_topic:
+            self.ranged_pub = compat.Publisher(self.ranged_topic, msgs.Detection2DArray, queue_size=1, bus=self.bus)
+            self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
+                                                self.pairer.push, queue_size=None, bus=self.bus)
         cb, qs = self._pc_callback, self.queue_size
         if self.batch > 1 or self.workers > 1:
             from .batching import MicroBatchRunner
@@ -160,6 +192,9 @@ class RosInference3D(BaseInference):
         if self.sub is not None:
             self.sub.unregister()
             self.sub = None
+        if self.camera_sub is not None:
+            self.camera_sub.unregister()
+            self.camera_sub = None
         if self.runner is not None:
             self.runner.close(drain=drain)
             self.runner = None
@@ -176,8 +211,12 @@ class RosInference3D(BaseInference):
     @staticmethod
     def _item(r: tuple) -> tuple:
         """What is published of one ``process`` (or :meth:`track`) result: (box message, picture or
-        None[, labelled cloud or None[, tracks message]])."""
-        return (r[0],) + (tuple(r[2:]) if len(r) > 2 else (None,))
+        None[, labelled cloud or None[, tracks message]]); a prediction that was ranged makes it
+        five long: (..., tracks message or None, ranged message or None)."""
+        item = (r[0],) + (tuple(r[2:]) if len(r) > 2 else (None,))
+        if isinstance(r[1], dict) and "ranged" in r[1]:
+            item = item + (None,) * (4 - len(item)) + (r[1]["ranged"],)
+        return item
 
     def _publish(self, item) -> None:
         m, im = item[0], item[1]
@@ -186,8 +225,10 @@ class RosInference3D(BaseInference):
             self.bev_pub.publish(im)
         if len(item) > 2 and item[2] is not None and self.points_pub is not None:
             self.points_pub.publish(item[2])
-        if len(item) > 3 and self.tracks_pub is not None:
+        if len(item) > 3 and item[3] is not None and self.tracks_pub is not None:
             self.tracks_pub.publish(item[3])
+        if len(item) > 4 and item[4] is not None and self.ranged_pub is not None:
+            self.ranged_pub.publish(item[4])
 
     def to_msg(self, pred: dict, header: msgs.Header):
         idx = select_boxes(pred, self.labels, self.score_thresh)
@@ -226,6 +267,9 @@ class RosInference3D(BaseInference):
         if self.points_topic:
             with timer("points_label"):
                 out = self._with_points(clouds, preds, out)
+        if self.ranged_topic:
+            with timer("range2d"):
+                self._range(clouds, preds)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -242,6 +286,16 @@ class RosInference3D(BaseInference):
         res = fn(clouds, preds, idx) if fn is not None else Detector3D.label_points(self.engine, clouds, preds, idx)
         return [(r[0], r[1], r[2] if len(r) > 2 else None, labelled_cloud(c, payload))
                 for r, c, (_, _, payload) in zip(out, clouds, res)]
+
+    def _range(self, clouds, preds) -> None:
+        """``pred["ranged"]`` of every cloud: its nearest camera message with ranges, None
+        without a partner within the slop.  One ranging call per batch."""
+        partners = [self.pairer.nearest(c.header.stamp, self.range_slop) for c in clouds]
+        fn = getattr(self.engine, "range_detections", None)  # (an engine that is no Detector3D subclass)
+        res = fn(clouds, partners, self.calibration, **self.range_options) if fn is not None else \
+            Detector3D.range_detections(self.engine, clouds, partners, self.calibration, **self.range_options)
+        for p, m in zip(preds, res):
+            p["ranged"] = m
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""
