@@ -54,20 +54,16 @@ the tracker; later ones get id 0.
 """
 from __future__ import annotations
 
-import os
-import threading
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
-import torch
 
 from .. import _native
+from .track_common import (HEADER, MAX_DETS, MAX_FRAMES, TrackerBase, TrackStateBase, device_enabled,  # noqa: F401
+                           frame_times, stamp_ns)
 
 MAX_CAPACITY = 1024  # kMaxCap in track3d.hip
-MAX_DETS = 512       # detections per frame: kMaxDets
-MAX_FRAMES = 64      # frames per launch: kMaxFrames
-HEADER = 4           # int32 words in front of the device state: next_id, overflow, 2 pad
 FIELDS = (("id", np.int32), ("label", np.int32), ("x", np.float32), ("y", np.float32), ("vx", np.float32),
           ("vy", np.float32), ("px", np.float32), ("py", np.float32), ("pt", np.float32), ("age", np.int32),
           ("hits", np.int32))  # the order of the device state's arrays
@@ -84,48 +80,10 @@ DEFAULT_MAX_DIST = 2.0
 F = np.float32
 
 
-def device_enabled() -> bool:
-    """``TCA_DEVICE_TRACK=0`` keeps the definition on GPU engines too."""
-    return os.environ.get("TCA_DEVICE_TRACK", "1") != "0"
-
-
 # ------------------------------------------------------------------------- definition
-class TrackState:
+class TrackState(TrackStateBase):
     """The tracker's state as host arrays (one per entry of :data:`FIELDS`)."""
-
-    def __init__(self, capacity: int):
-        capacity = int(capacity)
-        if not 1 <= capacity <= MAX_CAPACITY:
-            raise ValueError(f"capacity {capacity}: 1..{MAX_CAPACITY}")
-        self.capacity = capacity
-        for name, dt in FIELDS:
-            setattr(self, name, np.zeros(capacity, dt))
-        self.next_id = np.int32(1)
-        self.overflow = np.int32(0)
-
-    def words(self) -> np.ndarray:
-        """The device layout: int32 ``[HEADER + 11 * capacity]``."""
-        w = np.zeros(HEADER + len(FIELDS) * self.capacity, np.int32)
-        w[0], w[1] = self.next_id, self.overflow
-        for k, (name, _) in enumerate(FIELDS):
-            w[HEADER + k * self.capacity: HEADER + (k + 1) * self.capacity] = getattr(self, name).view(np.int32)
-        return w
-
-    @classmethod
-    def from_words(cls, w: np.ndarray, capacity: int) -> "TrackState":
-        st = cls(capacity)
-        w = np.ascontiguousarray(w, np.int32)
-        st.next_id, st.overflow = np.int32(w[0]), np.int32(w[1])
-        for k, (name, dt) in enumerate(FIELDS):
-            setattr(st, name, w[HEADER + k * capacity: HEADER + (k + 1) * capacity].view(dt).copy())
-        return st
-
-    def copy(self) -> "TrackState":
-        return TrackState.from_words(self.words(), self.capacity)
-
-    def same(self, other: "TrackState") -> bool:
-        """Bit for bit, ``next_id`` and ``overflow`` included."""
-        return self.capacity == other.capacity and bool((self.words() == other.words()).all())
+    FIELDS, MAX_CAPACITY = FIELDS, MAX_CAPACITY
 
 
 def gate_table(max_dist: Union[float, Dict[str, float], None] = None, names: Optional[Sequence[str]] = None,
@@ -170,12 +128,6 @@ def detection_rows(boxes, labels) -> np.ndarray:
     return rows
 
 
-def stamp_ns(stamp) -> int:
-    """Integer nanoseconds of a ``Time``, a header, or a number of nanoseconds."""
-    stamp = getattr(stamp, "stamp", stamp)
-    return int(stamp.to_nsec()) if hasattr(stamp, "to_nsec") else int(stamp)
-
-
 @dataclass
 class TrackBatch:
     """What :func:`track_table` makes of a batch of frames."""
@@ -192,23 +144,16 @@ def track_table(preds: Sequence[dict], idx: Optional[Sequence], stamps: Sequence
     """The per-frame inputs of a batch: ``preds[f]`` (``pred_boxes``, ``pred_labels``) selected by
     ``idx[f]`` (None: all), stamped ``stamps[f]``; ``prev_ns``: the stamp of the frame before the
     batch (None: the first frame ever)."""
-    gap_ns = int(round(float(max_gap) * 1e9))
-    rows, sent, dts, resets = [], [], [], []
+    rows, sent = [], []
     for f, p in enumerate(preds):
         sel = slice(None) if idx is None else np.asarray(idx[f], np.int64)
         r = detection_rows(np.asarray(p["pred_boxes"])[sel], np.asarray(p["pred_labels"])[sel])[:MAX_DETS]
         rows.append(r)
         sent.append(len(r))
-        now = stamp_ns(stamps[f])
-        d = 0 if prev_ns is None else now - prev_ns
-        rs = d < 0 or d > gap_ns
-        dts.append(np.float32(0.0) if rs else np.float32(np.float64(d) * 1e-9))
-        resets.append(1 if rs else 0)
-        prev_ns = now
+    dt, reset, last_ns = frame_times([stamps[f] for f in range(len(rows))], prev_ns, max_gap)
     return TrackBatch(rows=np.concatenate(rows) if rows else np.zeros(0, ROW_DTYPE),
                       det_off=np.concatenate([[0], np.cumsum(sent)]).astype(np.int32),
-                      dt=np.asarray(dts, np.float32).reshape(-1), reset=np.asarray(resets, np.uint8).reshape(-1),
-                      sent=sent, last_ns=prev_ns)
+                      dt=dt, reset=reset, sent=sent, last_ns=last_ns)
 
 
 def _gate(max_dist2: np.ndarray, label: int) -> np.float32:
@@ -289,10 +234,6 @@ def track_numpy(st: TrackState, batch: TrackBatch, max_dist2: np.ndarray, max_ag
 
 
 # --------------------------------------------------------------------------------- GPU
-def _align(n: int, a: int = 16) -> int:
-    return (n + a - 1) // a * a
-
-
 def launch(rows: int, det_off_host, n_frames: int, dt: int, reset: int, max_dist2: int, n_gates: int, state: int,
            capacity: int, max_age: int, alpha: float, out: int, stream=None) -> None:
     """The launch alone, on pointers (``det_off_host``: a host int32 array of ``n_frames + 1``
@@ -302,85 +243,27 @@ def launch(rows: int, det_off_host, n_frames: int, dt: int, reset: int, max_dist
                  max_age, float(alpha), out, _native.stream_ptr(stream))
 
 
-class Tracker3D:
+class Tracker3D(TrackerBase):
     """Tracks detections over frames: on a GPU with ``tca_track3d`` (its own stream, pinned
     staging and device state: one H2D of the rows, ``dt``, ``reset`` and gates, one launch and
     one D2H of the outputs per batch of up to :data:`MAX_FRAMES` frames), on the CPU and with
     ``TCA_DEVICE_TRACK=0`` with the definition.  ``max_dist``: metres, or a dict by class name
     of ``names`` (``label_base``: the label of ``names[0]``)."""
+    ENTRY, STATE = "tca_track3d", TrackState
 
     def __init__(self, capacity: int = 256, max_age: int = 3, max_dist: Union[float, Dict[str, float], None] = None,
                  max_gap: float = 2.0, alpha: float = 0.5, names: Optional[Sequence[str]] = None,
                  label_base: int = 1, device="cpu"):
-        self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device in (None, "auto") \
-            else torch.device(device)
-        self.gpu = self.device.type == "cuda" and device_enabled()
-        self.capacity, self.max_age, self.max_gap = int(capacity), int(max_age), float(max_gap)
         self.alpha = np.float32(alpha)
-        if self.max_age < 0:
-            raise ValueError("max_age: >= 0")
         self.max_dist2 = gate_table(max_dist, names, label_base)
-        self.prev_ns: Optional[int] = None
-        self.frames = 0
-        self._lock = threading.Lock()
-        self._host = TrackState(self.capacity)  # (validates the capacity)
-        self._pin_in = self._pin_out = self._dev_in = self._dev_out = self._stream = None
-        self._state = None
-        if self.gpu:
-            with torch.cuda.device(self.device):
-                self._stream = torch.cuda.Stream(self.device)
-                with torch.cuda.stream(self._stream):
-                    self._state = torch.from_numpy(self._host.words()).to(self.device)
-                self._stream.synchronize()
+        super().__init__(capacity, max_age, max_gap, device)
 
-    @property
-    def kind(self) -> str:
-        return "tca_track3d" if self.gpu else "host definition"
+    def _extra_inputs(self) -> List[np.ndarray]:
+        return [self.max_dist2]
 
-    # ------------------------------------------------------------------ staging
-    def _buf(self, name: str, nbytes: int, pinned: bool) -> torch.Tensor:
-        t = getattr(self, name)
-        if t is None or t.numel() < nbytes:
-            size = max(4096, 1 << (nbytes - 1).bit_length())
-            t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned \
-                else torch.empty((size,), dtype=torch.uint8, device=self.device)
-            setattr(self, name, t)
-        return t
-
-    def _run_device(self, b: TrackBatch) -> List[tuple]:
-        out: List[tuple] = []
-        with torch.cuda.device(self.device):
-            st = self._stream
-            for f0 in range(0, len(b.dt), MAX_FRAMES):
-                f1 = min(len(b.dt), f0 + MAX_FRAMES)
-                n0, n1 = int(b.det_off[f0]), int(b.det_off[f1])
-                nf, nd, ng = f1 - f0, n1 - n0, len(self.max_dist2)
-                o_dt = _align(32 * max(nd, 1))
-                o_reset = o_dt + _align(4 * nf)
-                o_gate = o_reset + _align(nf)
-                total = o_gate + _align(4 * ng)
-                pin = self._buf("_pin_in", total, True)
-                host = pin.numpy()
-                host[:32 * nd] = b.rows[n0:n1].view(np.uint8).reshape(-1)
-                host[o_dt:o_dt + 4 * nf] = b.dt[f0:f1].view(np.uint8)
-                host[o_reset:o_reset + nf] = b.reset[f0:f1]
-                host[o_gate:o_gate + 4 * ng] = self.max_dist2.view(np.uint8)
-                dev = self._buf("_dev_in", total, False)
-                res = self._buf("_dev_out", 16 * max(nd, 1), False)
-                pout = self._buf("_pin_out", 16 * max(nd, 1), True)
-                with torch.cuda.stream(st):
-                    dev[:total].copy_(pin[:total], non_blocking=True)
-                base = dev.data_ptr()
-                launch(base, b.det_off[f0:f1 + 1] - b.det_off[f0], nf, base + o_dt, base + o_reset, base + o_gate, ng,
-                       self._state.data_ptr(), self.capacity, self.max_age, self.alpha, res.data_ptr(), st)
-                with torch.cuda.stream(st):
-                    pout[:16 * nd].copy_(res[:16 * nd], non_blocking=True)
-                st.synchronize()
-                w = pout.numpy()[:16 * nd].view(np.int32).reshape(-1, 4).copy()
-                for f in range(f0, f1):
-                    r = w[int(b.det_off[f]) - n0:int(b.det_off[f + 1]) - n0]
-                    out.append((r[:, 0].copy(), r[:, 1].copy(), r[:, 2:4].copy().view(np.float32)))
-        return out
+    def _launch(self, rows, det_off, n_frames, dt, reset, extra, out) -> None:
+        launch(rows, det_off, n_frames, dt, reset, extra[0], len(self.max_dist2), self._state.data_ptr(), self.capacity,
+               self.max_age, self.alpha, out, self._stream)
 
     # ---------------------------------------------------------------------- API
     def track(self, preds: Sequence[dict], idx: Optional[Sequence], stamps: Sequence) -> List[tuple]:
@@ -400,15 +283,6 @@ class Tracker3D:
                 vel = np.pad(vel, ((0, n - len(vel)), (0, 0)))
             out.append((ids, hits, vel))
         return out
-
-    def state(self) -> TrackState:
-        """The state as host arrays (a copy)."""
-        with self._lock:
-            if not self.gpu:
-                return self._host.copy()
-            with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
-                w = self._state.cpu().numpy()
-            return TrackState.from_words(w, self.capacity)
 
 
 def parse_max_dist(text: Optional[str]) -> Union[float, Dict[str, float], None]:
