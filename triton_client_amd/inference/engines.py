@@ -130,36 +130,39 @@ class Detector3D(ABC):
                                         names, zo))
         return out
 
+    def _side_device(self):
+        """Where this engine's side ops run: ``label_device`` or ``device``, else ``"cpu"``."""
+        return getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
+
+    def _made_once(self, attr: str, make):
+        """``self.<attr>``, set to ``make(side device)`` when it is missing or None."""
+        obj = getattr(self, attr, None)
+        if obj is None:
+            obj = make(Detector3D._side_device(self))
+            setattr(self, attr, obj)
+        return obj
+
     def bev_painter(self) -> str:
         """``"device"`` when :meth:`render_bev` paints with ``tca_bev_render`` on this engine's
         GPU (``label_device`` / ``device``), ``"host"`` for an engine without one (the ring
         data-parallel engines among them) and with ``TCA_DEVICE_BEV=0``."""
         from ..ops.bev import device_enabled
 
-        dev = getattr(self, "label_device", None) or getattr(self, "device", None)
-        return "device" if dev is not None and torch.device(dev).type == "cuda" and device_enabled() else "host"
+        return "device" if torch.device(Detector3D._side_device(self)).type == "cuda" and device_enabled() else "host"
 
     def bev_renderer(self):
         """This engine's :class:`~triton_client_amd.ops.bev.BevRenderer`, made once like
         :meth:`point_labeler`."""
-        ren = getattr(self, "_bev_renderer", None)
-        if ren is None:
-            from ..ops.bev import BevRenderer
+        from ..ops.bev import BevRenderer
 
-            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
-            ren = self._bev_renderer = BevRenderer(dev)
-        return ren
+        return Detector3D._made_once(self, "_bev_renderer", BevRenderer)
 
     def point_labeler(self):
         """This engine's :class:`~triton_client_amd.ops.points_in_boxes.PointLabeler`: on the
         engine's GPU when it has one (``device`` / ``label_device``), else on the host."""
-        lab = getattr(self, "_point_labeler", None)
-        if lab is None:
-            from ..ops.points_in_boxes import PointLabeler
+        from ..ops.points_in_boxes import PointLabeler
 
-            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
-            lab = self._point_labeler = PointLabeler(dev)
-        return lab
+        return Detector3D._made_once(self, "_point_labeler", PointLabeler)
 
     def tracker(self, **options):
         """This engine's :class:`~triton_client_amd.ops.track3d.Tracker3D`, made once (the
@@ -168,8 +171,7 @@ class Detector3D(ABC):
         runs on rank 0's gathered results — with the host definition.  Gates are matched to this
         engine's class names; the CenterPoint family preloads the paper's nuScenes table, which a
         ``max_dist`` dict overrides by name and a ``max_dist`` number replaces."""
-        trk = getattr(self, "_tracker", None)
-        if trk is None:
+        def make(dev):
             from ..ops.track3d import CENTERPOINT_MAX_DIST, Tracker3D
 
             names = list(getattr(self, "names", None) or [])
@@ -178,22 +180,18 @@ class Detector3D(ABC):
                 have = {n.lower() for n in names}
                 md = {**{k: v for k, v in CENTERPOINT_MAX_DIST.items() if k in have},
                       **{str(k).lower(): v for k, v in (md or {}).items()}}
-            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
-            trk = self._tracker = Tracker3D(max_dist=md, names=names, label_base=getattr(self, "label_base", 1),
-                                            device=dev, **options)
-        return trk
+            return Tracker3D(max_dist=md, names=names, label_base=getattr(self, "label_base", 1), device=dev,
+                             **options)
+
+        return Detector3D._made_once(self, "_tracker", make)
 
     def ranger(self):
         """This engine's :class:`~triton_client_amd.ops.range2d.CameraRanger`, made once: on the
         engine's GPU when it has one (``label_device`` / ``device``; ``tca_range2d``), else — the
         ring data-parallel engines among them — with the host definition."""
-        rng = getattr(self, "_ranger", None)
-        if rng is None:
-            from ..ops.range2d import CameraRanger
+        from ..ops.range2d import CameraRanger
 
-            dev = getattr(self, "label_device", None) or getattr(self, "device", None) or "cpu"
-            rng = self._ranger = CameraRanger(dev)
-        return rng
+        return Detector3D._made_once(self, "_ranger", CameraRanger)
 
     def range_detections(self, clouds: Sequence[msgs.PointCloud2], detection_msgs: Sequence, calibration,
                          **options) -> List[Optional[msgs.Detection2DArray]]:

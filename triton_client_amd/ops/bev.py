@@ -19,12 +19,9 @@ formatting runs on the device.
 """
 from __future__ import annotations
 
-import contextlib
 import os
-import threading
-import warnings
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -33,7 +30,7 @@ from .. import _native
 from ..utils.bev import HEADING_COLOR, BevView, box_corners_px, label_color, render_bev_frame
 from ..utils.draw import label_text
 from ._ws import Workspace
-from .points_in_boxes import CloudLayout, _align, cloud_layout
+from .cloud_common import CloudLayout, CloudStager, _align, cloud_bytes, fields_f32
 
 ROW = 12  # int32 per box table row: kRow in bev_render.hip
 INT32_MAX = 2 ** 31 - 1
@@ -48,7 +45,7 @@ def device_enabled() -> bool:
 def device_takes(lay: CloudLayout) -> bool:
     """What ``tca_bev_render`` reads in place: little-endian FLOAT32 x, y, z and intensity
     inside the record (the painter's NaN-row rule needs the intensity field)."""
-    return lay.device_ok and lay.offsets[3] >= 0
+    return fields_f32(lay, (0, 1, 2, 3))
 
 
 def plane_words(view: BevView) -> int:
@@ -136,36 +133,19 @@ def _concat_tables(tables: Sequence[np.ndarray], texts: Sequence[bytes]) -> Tupl
     return tab, b"".join(texts), np.concatenate([[0], np.cumsum([len(t) for t in out])]).astype(np.int32)
 
 
-class BevRenderer:
+class BevRenderer(CloudStager):
     """Paints clouds and their predictions: on a GPU with ``tca_bev_render`` (its own
     workspace, stream and pinned staging: one H2D of payloads and tables, one launch, one
     D2H of the pictures per batch of same-layout clouds), on the CPU with the definition.
     Clouds the kernel does not take (non-FLOAT32 or big-endian fields, no intensity field)
     go to the host painter with one warning."""
 
-    def __init__(self, device="auto", ws: Optional[Workspace] = None):
-        self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device in (None, "auto") \
-            else torch.device(device)
-        self.gpu = self.device.type == "cuda"
-        self.ws = ws if ws is not None else (Workspace(self.device) if self.gpu else None)
-        self._lock = threading.Lock()
-        self._pin_in = self._pin_out = None
-        self._stream = None
-        self._warned = False
-
-    # ------------------------------------------------------------------ staging
-    def _pinned(self, name: str, nbytes: int) -> torch.Tensor:
-        t = getattr(self, name)
-        if t is None or t.numel() < nbytes:
-            t = torch.empty((max(4096, 1 << (nbytes - 1).bit_length()),), dtype=torch.uint8, pin_memory=True)
-            setattr(self, name, t)
-        return t
-
-    def _device_buf(self, name: str, nbytes: int) -> torch.Tensor:
-        cur = self.ws._bufs.get(name)
-        if cur is not None and cur.numel() >= nbytes:
-            return cur
-        return self.ws.get(name, (max(4096, 1 << (nbytes - 1).bit_length()),), torch.uint8)
+    @staticmethod
+    def sections(tab: np.ndarray, text: bytes, box_off: np.ndarray) -> list:
+        """What a batch stages after ``frame_off`` and ``frame_n``, in order (the arguments:
+        :func:`_concat_tables`)."""
+        return [("box_off", np.asarray(box_off, np.int32)), ("table", np.asarray(tab, np.int32)),
+                ("text", np.frombuffer(text, np.uint8))]
 
     def prepare(self, payloads: Sequence, ns: Sequence[int], layout: CloudLayout, tables: Sequence[np.ndarray],
                 texts: Sequence[bytes], view: BevView, z_offset: float = 0.0, stream=None,
@@ -182,64 +162,26 @@ class BevRenderer:
         K = len(tab)
         if B * plane_words(view) > INT32_MAX:
             raise ValueError(f"{B} pictures of {view.W}x{view.H} do not fit one call: split the batch")
-        step = layout.point_step
-        off, frame_off = 0, []
-        for n in ns:
-            frame_off.append(off + misalign)
-            off = _align(off + misalign + n * step)
-        data_bytes = off
-        sec = {}
-        for name, nbytes in (("frame_off", 8 * B), ("frame_n", 4 * B), ("box_off", 4 * (B + 1)),
-                             ("table", 4 * ROW * K), ("text", len(text))):
-            sec[name] = off
-            off = _align(off + max(nbytes, 4))
-        pin = self._pinned("_pin_in", off)
-        host = pin.numpy()
-        for pl, n, fo in zip(payloads, ns, frame_off):
-            if n:
-                host[fo:fo + n * step] = np.frombuffer(pl, np.uint8, n * step)
-
-        def put(name, a, dt):
-            a = np.ascontiguousarray(a, dt).reshape(-1)
-            host[sec[name]:sec[name] + a.nbytes] = a.view(np.uint8)
-
-        put("frame_off", frame_off, np.int64)
-        put("frame_n", ns, np.int32)
-        put("box_off", box_off, np.int32)
-        put("table", tab, np.int32)
-        put("text", np.frombuffer(text, np.uint8), np.uint8)
-        dev = self._device_buf("bev_in", off)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            dev[:off].copy_(pin[:off], non_blocking=True)
-
-        def dview(name, count, dt):
-            return dev[sec[name]:sec[name] + max(count, 1) * dt.itemsize].view(dt)
-
+        dev, plan, dview = self._stage("bev_in", payloads, ns, layout.point_step, misalign,
+                                       self.sections(tab, text, box_off), stream)
         H, W = view.H, view.W
         words = max(B, 1) * plane_words(view)
         plane = self._device_buf("bev_plane", 4 * words)[:4 * words].view(torch.int32)
         out = self._device_buf("bev_out", max(B, 1) * H * W * 3)[:B * H * W * 3].view(B, H, W, 3)
-        return BevCall(data=dev, data_bytes=data_bytes, frame_off=dview("frame_off", B, torch.int64),
+        return BevCall(data=dev, data_bytes=plan.data_bytes, frame_off=dview("frame_off", B, torch.int64),
                        frame_n=dview("frame_n", B, torch.int32), box_off=dview("box_off", B + 1, torch.int32),
                        table=dview("table", ROW * K, torch.int32), text=dview("text", len(text), torch.uint8),
                        plane=plane, out=out, layout=layout, consts=_consts(view, z_offset), batch=B,
-                       max_n=max(ns, default=0), n_boxes=K, text_bytes=len(text), frame_offs=tuple(frame_off))
+                       max_n=max(ns, default=0), n_boxes=K, text_bytes=len(text), frame_offs=plan.frame_offs)
 
     launch = staticmethod(launch)
 
     def _run_device(self, payloads, ns, layout, tables, texts, view, z_offset) -> List[np.ndarray]:
         with torch.cuda.device(self.device):
-            if self._stream is None:
-                self._stream = torch.cuda.Stream(self.device)
-            st = self._stream
+            st = self._own_stream()
             c = self.prepare(payloads, ns, layout, tables, texts, view, z_offset, st)
             launch(c, st)
-            nbytes = c.out.numel()
-            pin = self._pinned("_pin_out", nbytes)
-            with torch.cuda.stream(st):
-                pin[:nbytes].copy_(c.out.reshape(-1), non_blocking=True)
-            st.synchronize()
-        host = pin.numpy()[:nbytes].reshape(c.out.shape)
+            host = self._fetch(c.out.reshape(-1), c.out.numel(), st).reshape(c.out.shape)
         return [host[b].copy() for b in range(c.batch)]
 
     # ---------------------------------------------------------------------- API
@@ -248,28 +190,16 @@ class BevRenderer:
         """Per cloud the uint8 [H, W, 3] picture of ``cloud_to_numpy(cloud, z_offset=z_offset)``
         and ``preds[b]`` (``pred_boxes``, ``pred_scores``, ``pred_labels``) — what
         ``render_bev_frame(..., view, names, z_offset)`` paints."""
-        out: List[Optional[np.ndarray]] = [None] * len(clouds)
-        groups = {}
-        for i, c in enumerate(clouds):
-            lay = cloud_layout(c) if self.gpu else None
-            if self.gpu and device_takes(lay):
-                groups.setdefault(lay, []).append(i)
-                continue
-            if self.gpu and not self._warned:
-                self._warned = True
-                warnings.warn(f"BevRenderer: tca_bev_render takes little-endian FLOAT32 x, y, z and intensity only "
-                              f"(got {lay}); such clouds are painted on the host", RuntimeWarning, stacklevel=2)
-            out[i] = render_host(c, preds[i], view, names, z_offset)
-        for lay, idx in groups.items():
+        def group_args(lay, idx):
             tt = [bev_box_table(preds[i]["pred_boxes"], preds[i]["pred_scores"], preds[i]["pred_labels"], None, view,
                                 names) for i in idx]
-            with self._lock:
-                res = self._run_device([clouds[i].data for i in idx],
-                                       [int(clouds[i].width) * int(clouds[i].height) for i in idx], lay,
-                                       [t for t, _ in tt], [s for _, s in tt], view, z_offset)
-            for i, r in zip(idx, res):
-                out[i] = r
-        return out
+            return (*cloud_bytes(clouds, idx), lay, [t for t, _ in tt], [s for _, s in tt], view, z_offset)
+
+        return self._per_cloud(
+            clouds, lambda i, lay: device_takes(lay),
+            lambda i, lay: render_host(clouds[i], preds[i], view, names, z_offset), group_args, self._run_device,
+            lambda i, lay: f"BevRenderer: tca_bev_render takes little-endian FLOAT32 x, y, z and intensity only "
+                           f"(got {lay}); such clouds are painted on the host", host_layouts=False)
 
 
 def render_host(cloud, pred: dict, view: BevView, names=None, z_offset: float = 0.0) -> np.ndarray:

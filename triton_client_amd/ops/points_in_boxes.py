@@ -33,9 +33,6 @@ an intensity field), ``label`` int32 (the owner's class, 0 for background),
 """
 from __future__ import annotations
 
-import contextlib
-import threading
-import warnings
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -44,8 +41,9 @@ import torch
 
 from .. import _native
 from ..ros import msgs
-from ._ws import Workspace
 from .box3d import boxes7
+from .cloud_common import (_PF_NP, CloudLayout, CloudStager, _align, cloud_bytes, cloud_layout,  # noqa: F401
+                           cloud_xyzi, flat)
 
 CHUNK = 128  # boxes per LDS stage: kChunk in points_in_boxes.hip
 RECORD = 28  # bytes per labelled point
@@ -173,65 +171,6 @@ def pack_records(xyzi: np.ndarray, owner: np.ndarray, scores, labels) -> np.ndar
     return rec
 
 
-# ------------------------------------------------------------------------------ clouds
-_PF_NP = {1: "i1", 2: "u1", 3: "<i2", 4: "<u2", 5: "<i4", 6: "<u4", 7: "<f4", 8: "<f8"}
-
-
-@dataclass(frozen=True)
-class CloudLayout:
-    """Where x, y, z and intensity (offset -1: none) lie in a point record."""
-    point_step: int
-    offsets: Tuple[int, int, int, int]
-    dtypes: Tuple[int, int, int, int]
-    bigendian: bool = False
-
-    @property
-    def device_ok(self) -> bool:
-        """What ``tca_points_in_boxes`` takes: little-endian FLOAT32 fields inside the record."""
-        if self.bigendian or self.point_step <= 0:
-            return False
-        for j, (o, d) in enumerate(zip(self.offsets, self.dtypes)):
-            if j == 3 and o < 0:
-                continue
-            if d != 7 or o < 0 or o + 4 > self.point_step:
-                return False
-        return True
-
-
-def cloud_layout(msg) -> CloudLayout:
-    by = {f.name: f for f in msg.fields}
-    missing = [n for n in ("x", "y", "z") if n not in by]
-    if missing:
-        raise ValueError(f"PointCloud2 lacks fields {missing}")
-    f = [by["x"], by["y"], by["z"], by.get("intensity")]
-    return CloudLayout(int(msg.point_step), tuple(-1 if g is None else int(g.offset) for g in f),
-                       tuple(7 if g is None else int(g.datatype) for g in f), bool(msg.is_bigendian))
-
-
-def cloud_xyzi(msg, lay: Optional[CloudLayout] = None) -> np.ndarray:
-    """[N, 4] float32 x, y, z, intensity of every point of the message, in input order, NaN
-    points included (FLOAT32 fields keep their bits; 0 without an intensity field)."""
-    lay = lay or cloud_layout(msg)
-    n = int(msg.width) * int(msg.height)
-    out = np.zeros((n, 4), np.float32)
-    if n == 0:
-        return out
-    use = [j for j in range(4) if lay.offsets[j] >= 0]
-    fmt = [_PF_NP[lay.dtypes[j]] for j in use]
-    if lay.bigendian:
-        fmt = [f.replace("<", ">") for f in fmt]
-    dt = np.dtype({"names": [str(j) for j in use], "formats": fmt, "offsets": [lay.offsets[j] for j in use],
-                   "itemsize": lay.point_step})
-    rec = np.frombuffer(msg.data, dtype=dt, count=n)
-    for j in use:
-        col = rec[str(j)]
-        if lay.dtypes[j] == 7 and not lay.bigendian:
-            out.view(np.uint32)[:, j] = col.view(np.uint32)
-        else:
-            out[:, j] = col
-    return out
-
-
 def labelled_cloud(cloud, payload) -> msgs.PointCloud2:
     """The published message: the cloud's header, height, width and is_dense, 28-byte records."""
     return msgs.PointCloud2(header=cloud.header, height=cloud.height, width=cloud.width, fields=list(LABEL_FIELDS),
@@ -240,10 +179,6 @@ def labelled_cloud(cloud, payload) -> msgs.PointCloud2:
 
 
 # --------------------------------------------------------------------------------- GPU
-def _align(n: int, a: int = 16) -> int:
-    return (n + a - 1) // a * a
-
-
 @dataclass
 class LabelCall:
     """One prepared launch: device views of its inputs and outputs."""
@@ -277,36 +212,26 @@ def launch(c: LabelCall, stream=None) -> None:
                  c.n_boxes, p(c.pt_off), p(c.owner), p(c.count), p(c.record), _native.stream_ptr(stream))
 
 
-class PointLabeler:
+def out_sections(total: int, n_boxes: int) -> Tuple[int, int, int]:
+    """Byte offsets of owner, count and record in the output buffer of ``total`` points."""
+    o_count = _align(4 * max(total, 1))
+    return 0, o_count, o_count + _align(4 * max(n_boxes, 1))
+
+
+class PointLabeler(CloudStager):
     """Labels clouds against boxes: on a GPU with ``tca_points_in_boxes`` (its own
     workspace, stream and pinned staging: one H2D of payloads and tables, one launch,
     one D2H of owners, counts and records per batch of same-layout clouds), on the CPU
     with the definition.  Clouds the kernel does not take (non-FLOAT32 or big-endian
     fields) run the definition with one warning."""
 
-    def __init__(self, device="auto", ws: Optional[Workspace] = None):
-        self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device in (None, "auto") \
-            else torch.device(device)
-        self.gpu = self.device.type == "cuda"
-        self.ws = ws if ws is not None else (Workspace(self.device) if self.gpu else None)
-        self._lock = threading.Lock()
-        self._pin_in = self._pin_out = None
-        self._stream = None
-        self._warned = False
-
-    # ------------------------------------------------------------------ staging
-    def _pinned(self, name: str, nbytes: int) -> torch.Tensor:
-        t = getattr(self, name)
-        if t is None or t.numel() < nbytes:
-            t = torch.empty((max(4096, 1 << (nbytes - 1).bit_length()),), dtype=torch.uint8, pin_memory=True)
-            setattr(self, name, t)
-        return t
-
-    def _device_buf(self, name: str, nbytes: int) -> torch.Tensor:
-        cur = self.ws._bufs.get(name)
-        if cur is not None and cur.numel() >= nbytes:
-            return cur
-        return self.ws.get(name, (max(4096, 1 << (nbytes - 1).bit_length()),), torch.uint8)
+    @staticmethod
+    def sections(ns: Sequence[int], tables: Sequence, scores: Sequence, labels: Sequence) -> list:
+        """What a batch stages after ``frame_off`` and ``frame_n``, in order."""
+        return [("box_off", np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int32)),
+                ("pt_off", np.concatenate([[0], np.cumsum(ns)]).astype(np.int32)),
+                ("table", flat(tables, np.float32)), ("score", flat(scores, np.float32)),
+                ("label", flat(labels, np.int32))]
 
     def prepare(self, payloads: Sequence, ns: Sequence[int], layout: CloudLayout, tables: Sequence[np.ndarray],
                 scores: Sequence[np.ndarray], labels: Sequence[np.ndarray], records: bool = True,
@@ -319,50 +244,13 @@ class PointLabeler:
             raise ValueError(f"tca_points_in_boxes does not take this layout: {layout}")
         B = len(payloads)
         ns = [int(n) for n in ns]
-        nb = [len(t) for t in tables]
-        K, total = sum(nb), sum(ns)
+        K, total = sum(len(t) for t in tables), sum(ns)
         if total > INT32_MAX // RECORD:
             raise ValueError(f"{total} points do not fit the int32 offsets of one call: split the batch")
-        step = layout.point_step
-        off, frame_off = 0, []
-        for n in ns:
-            frame_off.append(off + misalign)
-            off = _align(off + misalign + n * step)
-        sec = {}
-        for name, nbytes in (("frame_off", 8 * B), ("frame_n", 4 * B), ("box_off", 4 * (B + 1)),
-                             ("pt_off", 4 * (B + 1)), ("table", 32 * K), ("score", 4 * K), ("label", 4 * K)):
-            sec[name] = off
-            off = _align(off + max(nbytes, 4))
-        pin = self._pinned("_pin_in", off)
-        host = pin.numpy()
-        for pl, n, fo in zip(payloads, ns, frame_off):
-            if n:
-                host[fo:fo + n * step] = np.frombuffer(pl, np.uint8, n * step)
-
-        def put(name, a, dt):
-            a = np.ascontiguousarray(a, dt).reshape(-1)
-            host[sec[name]:sec[name] + a.nbytes] = a.view(np.uint8)
-
-        put("frame_off", frame_off, np.int64)
-        put("frame_n", ns, np.int32)
-        put("box_off", np.concatenate([[0], np.cumsum(nb)]), np.int32)
-        put("pt_off", np.concatenate([[0], np.cumsum(ns)]), np.int32)
-        if K:
-            put("table", np.concatenate([np.asarray(t, np.float32).reshape(-1, 8) for t in tables]), np.float32)
-            put("score", np.concatenate([np.asarray(s, np.float32).reshape(-1) for s in scores]), np.float32)
-            put("label", np.concatenate([np.asarray(v).reshape(-1).astype(np.int32) for v in labels]), np.int32)
-        dev = self._device_buf("pib_in", off)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            dev[:off].copy_(pin[:off], non_blocking=True)
-
-        def view(name, count, dt):
-            return dev[sec[name]:sec[name] + max(count, 1) * dt.itemsize].view(dt)
-
-        o_owner = 0
-        o_count = _align(4 * max(total, 1))
-        o_rec = o_count + _align(4 * max(K, 1))
-        out_bytes = o_rec + (RECORD * max(total, 1) if records else 0)
-        out = self._device_buf("pib_out", out_bytes)
+        dev, _, view = self._stage("pib_in", payloads, ns, layout.point_step, misalign,
+                                   self.sections(ns, tables, scores, labels), stream)
+        o_owner, o_count, o_rec = out_sections(total, K)
+        out = self._device_buf("pib_out", o_rec + (RECORD * max(total, 1) if records else 0))
         i32, f32, i64 = torch.int32, torch.float32, torch.int64
         return LabelCall(
             data=dev, frame_off=view("frame_off", B, i64), frame_n=view("frame_n", B, i32),
@@ -379,17 +267,10 @@ class PointLabeler:
     def _run_device(self, payloads, ns, layout, tables, scores, labels):
         """→ per frame (owner, count, payload bytes)."""
         with torch.cuda.device(self.device):
-            if self._stream is None:
-                self._stream = torch.cuda.Stream(self.device)
-            st = self._stream
+            st = self._own_stream()
             c = self.prepare(payloads, ns, layout, tables, scores, labels, True, st)
             launch(c, st)
-            nbytes = c.out_sections[2] + RECORD * c.total
-            pin = self._pinned("_pin_out", nbytes)
-            with torch.cuda.stream(st):
-                pin[:nbytes].copy_(c.out[:nbytes], non_blocking=True)
-            st.synchronize()
-        host = pin.numpy()
+            host = self._fetch(c.out, c.out_sections[2] + RECORD * c.total, st)
         owner = host[:4 * c.total].view(np.int32)
         count = host[c.out_sections[1]:c.out_sections[1] + 4 * c.n_boxes].view(np.int32)
         rec = host[c.out_sections[2]:c.out_sections[2] + RECORD * c.total]
@@ -405,29 +286,16 @@ class PointLabeler:
         """Per cloud ``(owner [N] int32, count [K] int32, payload)``: ``payload`` is the bytes of
         the labelled cloud's 28-byte records (:func:`labelled_cloud`).  ``boxes[b]`` [K, 7 or 9],
         ``scores[b]`` [K] and ``labels[b]`` [K] belong to ``clouds[b]``."""
-        lays = [cloud_layout(c) for c in clouds]
-        out: List[Optional[tuple]] = [None] * len(clouds)
-        groups = {}
-        for i, lay in enumerate(lays):
-            if self.gpu and lay.device_ok:
-                groups.setdefault(lay, []).append(i)
-                continue
-            if self.gpu and not self._warned:
-                self._warned = True
-                warnings.warn(f"PointLabeler: tca_points_in_boxes takes little-endian FLOAT32 x, y, z and intensity "
-                              f"only (got {lay}); such clouds are labelled on the host", RuntimeWarning,
-                              stacklevel=2)
-            out[i] = label_numpy(clouds[i], boxes[i], scores[i], labels[i], lay)
-        for lay, idx in groups.items():
-            tabs = [box_table(boxes[i], scores[i]) for i in idx]
-            with self._lock:
-                res = self._run_device([clouds[i].data for i in idx],
-                                       [int(clouds[i].width) * int(clouds[i].height) for i in idx], lay, tabs,
-                                       [np.asarray(scores[i], np.float32).reshape(-1) for i in idx],
-                                       [np.asarray(labels[i]).reshape(-1) for i in idx])
-            for i, r in zip(idx, res):
-                out[i] = r
-        return out
+        def group_args(lay, idx):
+            return (*cloud_bytes(clouds, idx), lay, [box_table(boxes[i], scores[i]) for i in idx],
+                    [np.asarray(scores[i], np.float32).reshape(-1) for i in idx],
+                    [np.asarray(labels[i]).reshape(-1) for i in idx])
+
+        return self._per_cloud(
+            clouds, lambda i, lay: lay.device_ok,
+            lambda i, lay: label_numpy(clouds[i], boxes[i], scores[i], labels[i], lay), group_args, self._run_device,
+            lambda i, lay: f"PointLabeler: tca_points_in_boxes takes little-endian FLOAT32 x, y, z and intensity "
+                           f"only (got {lay}); such clouds are labelled on the host")
 
     def count_points(self, cloud, boxes) -> np.ndarray:
         """Points of ``cloud`` inside each of ``boxes`` [K, 7] (every box scores 0)."""

@@ -50,11 +50,9 @@ half to even).
 """
 from __future__ import annotations
 
-import contextlib
 import copy
 import os
 import threading
-import warnings
 from collections import deque
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -64,8 +62,7 @@ import torch
 
 from .. import _native
 from ..ros import msgs
-from ._ws import Workspace
-from .points_in_boxes import CloudLayout, _align, cloud_layout, cloud_xyzi
+from .cloud_common import CloudLayout, CloudStager, _align, cloud_bytes, cloud_xyzi, fields_f32, flat, plan_staging
 
 NB = 512  # depth bins: kBins in range2d.hip
 MAX_FRAMES = 64  # clouds per launch
@@ -456,12 +453,10 @@ def unpack(out: np.ndarray, k: int):
 
 def layout_device_ok(lay: CloudLayout) -> bool:
     """What ``tca_range2d`` reads in place: little-endian FLOAT32 x, y, z inside the record."""
-    if lay.bigendian or lay.point_step <= 0:
-        return False
-    return all(d == 7 and 0 <= o and o + 4 <= lay.point_step for o, d in zip(lay.offsets[:3], lay.dtypes[:3]))
+    return fields_f32(lay, (0, 1, 2))
 
 
-class CameraRanger:
+class CameraRanger(CloudStager):
     """Ranges pixel boxes against clouds: on a GPU with ``tca_range2d`` (its own workspace,
     stream and pinned staging: one H2D of payloads and rows, one launch, one D2H of the
     per-box integers per batch of same-layout clouds), on the CPU — and with
@@ -469,29 +464,10 @@ class CameraRanger:
     (non-FLOAT32 or big-endian fields, more than 512 boxes) run the definition with one
     warning."""
 
-    def __init__(self, device="auto", ws: Optional[Workspace] = None):
-        self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device in (None, "auto") \
-            else torch.device(device)
-        self.gpu = self.device.type == "cuda"
-        self.ws = ws if ws is not None else (Workspace(self.device) if self.gpu else None)
-        self._lock = threading.Lock()
-        self._pin_in = self._pin_out = None
-        self._stream = None
-        self._warned = False
-
-    # ------------------------------------------------------------------ staging
-    def _pinned(self, name: str, nbytes: int) -> torch.Tensor:
-        t = getattr(self, name)
-        if t is None or t.numel() < nbytes:
-            t = torch.empty((max(4096, 1 << (nbytes - 1).bit_length()),), dtype=torch.uint8, pin_memory=True)
-            setattr(self, name, t)
-        return t
-
-    def _device_buf(self, name: str, nbytes: int) -> torch.Tensor:
-        cur = self.ws._bufs.get(name)
-        if cur is not None and cur.numel() >= nbytes:
-            return cur
-        return self.ws.get(name, (max(4096, 1 << (nbytes - 1).bit_length()),), torch.uint8)
+    @staticmethod
+    def sections(rows: Sequence[np.ndarray]) -> list:
+        """What a batch stages after ``frame_off`` and ``frame_n``."""
+        return [("table", flat(rows, np.float32))]
 
     def prepare(self, payloads: Sequence, ns: Sequence[int], layout: CloudLayout, rows: Sequence[np.ndarray], M,
                 opts: Optional[RangeOptions] = None, stream=None, misalign: int = 0) -> RangeCall:
@@ -505,39 +481,10 @@ class CameraRanger:
         ns = [int(n) for n in ns]
         nb = [len(t) for t in rows]
         K = sum(nb)
-        step = layout.point_step
-        off, frame_off = 0, []
-        for n in ns:
-            frame_off.append(off + misalign)
-            off = _align(off + misalign + n * step)
-        data_bytes = off
+        data_bytes = plan_staging(ns, layout.point_step, misalign, ()).data_bytes  # (refused before any allocation)
         if data_bytes >= INT31:
             raise ValueError(f"{data_bytes} payload bytes do not fit one call: split the batch")
-        sec = {}
-        for name, nbytes in (("frame_off", 8 * B), ("frame_n", 4 * B), ("table", 16 * K)):
-            sec[name] = off
-            off = _align(off + max(nbytes, 4))
-        pin = self._pinned("_pin_in", off)
-        host = pin.numpy()
-        for pl, n, fo in zip(payloads, ns, frame_off):
-            if n:
-                host[fo:fo + n * step] = np.frombuffer(pl, np.uint8, n * step)
-
-        def put(name, a, dt):
-            a = np.ascontiguousarray(a, dt).reshape(-1)
-            host[sec[name]:sec[name] + a.nbytes] = a.view(np.uint8)
-
-        put("frame_off", frame_off, np.int64)
-        put("frame_n", ns, np.int32)
-        if K:
-            put("table", np.concatenate([np.asarray(t, np.float32).reshape(-1, 4) for t in rows]), np.float32)
-        dev = self._device_buf("r2d_in", off)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            dev[:off].copy_(pin[:off], non_blocking=True)
-
-        def view(name, count, dt):
-            return dev[sec[name]:sec[name] + max(count, 1) * dt.itemsize].view(dt)
-
+        dev, _, view = self._stage("r2d_in", payloads, ns, layout.point_step, misalign, self.sections(rows), stream)
         hist = self._device_buf("r2d_hist", 4 * NB * max(K, 1))
         out = self._device_buf("r2d_out", 4 * OUT_INTS * max(K, 1))
         return RangeCall(data=dev, data_bytes=data_bytes, frame_off=view("frame_off", B, torch.int64),
@@ -551,18 +498,15 @@ class CameraRanger:
     def _run_device(self, payloads, ns, layout, rows, M, opts):
         """→ per frame ``(n, m, c, sums)``."""
         with torch.cuda.device(self.device):
-            if self._stream is None:
-                self._stream = torch.cuda.Stream(self.device)
-            st = self._stream
+            st = self._own_stream()
             c = self.prepare(payloads, ns, layout, rows, M, opts, st)
-            nbytes = 4 * OUT_INTS * c.n_boxes
             if c.n_boxes:
                 launch(c, st)
-                pin = self._pinned("_pin_out", nbytes)
-                with torch.cuda.stream(st):
-                    pin[:nbytes].copy_(c.out[:nbytes], non_blocking=True)
-            st.synchronize()
-        n, m, cc, sums = unpack(pin.numpy()[:nbytes], c.n_boxes) if c.n_boxes else unpack(np.zeros(0, np.int32), 0)
+                host = self._fetch(c.out, 4 * OUT_INTS * c.n_boxes, st)
+            else:  # nothing to range: no launch, no D2H
+                st.synchronize()
+                host = np.zeros(0, np.int32)
+        n, m, cc, sums = unpack(host, c.n_boxes)
         out, ko = [], 0
         for t in rows:
             k = len(t)
@@ -570,33 +514,20 @@ class CameraRanger:
             ko += k
         return out
 
+    def _parts(self, idx, clouds):
+        return _launch_groups(idx, [len(clouds[i].data) for i in idx])
+
     # ---------------------------------------------------------------------- API
     def range(self, clouds: Sequence, rows: Sequence[np.ndarray], M, opts: Optional[RangeOptions] = None) -> List[tuple]:
         """Per cloud ``(n, m, c, sums)`` of its ``rows[b]`` (:func:`box_rows`) under ``M``."""
         opts = opts or RangeOptions()
-        lays = [cloud_layout(c) for c in clouds]
-        out: List[Optional[tuple]] = [None] * len(clouds)
-        groups = {}
-        device = self.gpu and device_enabled()
-        for i, lay in enumerate(lays):
-            if device and layout_device_ok(lay) and len(rows[i]) <= MAX_BOXES:
-                groups.setdefault(lay, []).append(i)
-                continue
-            if device and not self._warned:
-                self._warned = True
-                warnings.warn(f"CameraRanger: tca_range2d takes little-endian FLOAT32 x, y, z and at most "
-                              f"{MAX_BOXES} boxes per cloud (got {lay}, {len(rows[i])} boxes); such clouds are "
-                              f"ranged on the host", RuntimeWarning, stacklevel=2)
-            out[i] = range_numpy(clouds[i], rows[i], M, opts, lay)
-        for lay, idx in groups.items():
-            for part in _launch_groups(idx, [len(clouds[i].data) for i in idx]):
-                with self._lock:
-                    res = self._run_device([clouds[i].data for i in part],
-                                           [int(clouds[i].width) * int(clouds[i].height) for i in part], lay,
-                                           [rows[i] for i in part], M, opts)
-                for i, r in zip(part, res):
-                    out[i] = r
-        return out
+        return self._per_cloud(
+            clouds, lambda i, lay: layout_device_ok(lay) and len(rows[i]) <= MAX_BOXES,
+            lambda i, lay: range_numpy(clouds[i], rows[i], M, opts, lay),
+            lambda lay, part: (*cloud_bytes(clouds, part), lay, [rows[i] for i in part], M, opts), self._run_device,
+            lambda i, lay: f"CameraRanger: tca_range2d takes little-endian FLOAT32 x, y, z and at most {MAX_BOXES} "
+                           f"boxes per cloud (got {lay}, {len(rows[i])} boxes); such clouds are ranged on the host",
+            device=self.gpu and device_enabled())
 
 
 def _launch_groups(idx: Sequence[int], nbytes: Sequence[int]):
