@@ -1,6 +1,6 @@
 // Reading a point's FLOAT32 fields out of raw PointCloud2 bytes in place: the three load
 // paths of K22 (points in boxes) and K23 (bird's-eye view), as a header for K26 (camera
-// ranging) and later kernels.  K22 and K23 keep their own text of the same statements: calling
+// ranging), K27 (depth image) and later kernels.  K22 and K23 keep their own text of the same statements: calling
 // these helpers instead changes their register allocation, and their code objects are to stay
 // as they are.
 //

@@ -111,6 +111,10 @@ def main():
     ap.add_argument("--ranged", action="store_true",
                     help="LiDAR side: also range 64 synthetic camera detections per cloud, stamped like the cloud, "
                          "under a fixed KITTI-like calibration (RosInference3D ranged_topic)")
+    ap.add_argument("--depth", action="store_true",
+                    help="LiDAR side: also publish every cloud as a 16UC1 depth Image of --depth-size pixels under a "
+                         "fixed KITTI-like calibration rescaled to that size (RosInference3D depth_topic)")
+    ap.add_argument("--depth-size", default="1280x720", metavar="WxH")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -126,6 +130,8 @@ def main():
     ap.add_argument("--wire", choices=["raw", "proto", "shm", "devshm"], default="raw",
                     help="remote: request codec / transport (shm, devshm: shared-memory regions, server on this node)")
     a = ap.parse_args()
+    if a.depth and a.ranged:
+        ap.error("--depth rescales the calibration that --ranged uses as it is: run them apart")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # self-launch (a child: nothing has touched the GPU)
         import socket
         import subprocess
@@ -227,20 +233,27 @@ def main():
                              **({"points_topic": "/pc_points"} if a.points else {}),
                              **({"tracks_topic": "/pc_tracks"} if a.tracks else {}),
                              **({"ranged_topic": "/cam_ranged", "camera_detections_topic": "/cam_det",
-                                 "calibration": _kitti_like_calibration()} if a.ranged else {}))
+                                 "calibration": _kitti_like_calibration()} if a.ranged else {}),
+                             **(_depth_arguments(a) if a.depth else {}))
         dets = _detection_messages(msgs_in) if a.ranged else None
         ranged = []
         rsub = compat.Subscriber("/cam_ranged", msgs.Detection2DArray, ranged.append, bus=bus) if a.ranged else None
+        depth = []
+        dsub = compat.Subscriber("/pc_depth", msgs.Image, lambda m: depth.append(len(m.data)), bus=bus) \
+            if a.depth else None
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout,
              side=("/cam_det", dets[:warm]) if dets else None)
         st.sum.clear(), st.n.clear()
         del ranged[:]
+        del depth[:]
         n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout,
                          side=("/cam_det", dets[warm:]) if dets else None)
         drv.stop()
         if rsub is not None:
             rsub.unregister()
+        if dsub is not None:
+            dsub.unregister()
         if info is not None:
             eng3.close()
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
@@ -263,6 +276,15 @@ def main():
             out["lidar"]["ranger"] = kind
             out["lidar"]["ranged"] = {"messages": len(ranged), "detections": sum(len(m.detections) for m in ranged),
                                       "with_range": got}
+        if a.depth:
+            from triton_client_amd.inference.engines import Detector3D
+            from triton_client_amd.ops.depth_image import device_enabled
+            kind = "tca_depth_image" if Detector3D.depth_imager(eng3).gpu and device_enabled() else "host definition"
+            o = drv.depth_options
+            print(f"depth images: {kind}", file=sys.stderr)
+            out["lidar"]["output"] += f" + depth Image {o.encoding} {o.width}x{o.height} ({kind})"
+            out["lidar"]["depth_imager"] = kind
+            out["lidar"]["depth"] = {"messages": len(depth), "bytes_per_image": round(sum(depth) / max(1, len(depth)))}
         if a.tracks:
             trk = drv.tracker()
             ts = trk.state()
@@ -316,6 +338,18 @@ def _kitti_like_calibration():
     P = [[721.5377, 0.0, 609.5593, 44.85728], [0.0, 721.5377, 172.854, 0.2163791], [0.0, 0.0, 1.0, 0.002745884]]
     T = [[0.0, -1.0, 0.0, 0.0], [0.0, 0.0, -1.0, -0.08], [1.0, 0.0, 0.0, -0.27], [0.0, 0.0, 0.0, 1.0]]
     return Calibration(np.array(P), np.array(T))
+
+
+def _depth_arguments(a):
+    """The driver's depth arguments: the KITTI-like rig with its 1242 x 375 projection rescaled to
+    --depth-size, the default options."""
+    from triton_client_amd.ops.depth_image import DepthOptions
+    from triton_client_amd.ops.range2d import Calibration
+
+    w, h = (int(v) for v in a.depth_size.lower().split("x"))
+    cal = _kitti_like_calibration()
+    P = np.diag([w / 1242.0, h / 375.0, 1.0]) @ cal.P
+    return {"depth_topic": "/pc_depth", "depth_options": DepthOptions(w, h), "calibration": Calibration(P, cal.T)}
 
 
 def _detection_messages(clouds, per_cloud=64):

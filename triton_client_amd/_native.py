@@ -85,6 +85,9 @@ _KERNEL_SIGS = {
     # min_depth, pct, min_points, window, hist, out, stream (csrc/kernels/range2d.hip)
     "tca_range2d": [P, L, P, P, I, I, I, I, I, I, P, P, P, F, F, I, I, I, P, P, P],
     "tca_range2d_bins": [],  # returns the depth bins per box (not an error code)
+    # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z, M (host), W, H, encoding (0: 16UC1,
+    # 1: 32FC1), scale, min_depth, splat, plane, out, stream (csrc/kernels/depth_image.hip)
+    "tca_depth_image": [P, L, P, P, I, I, I, I, I, I, P, I, I, I, F, F, I, P, P, P],
     "tca_nms_merge": [P, P, P, P, P, P, P, P, I, I, I, F, I, I, P, P, P, P, P, P],
     "tca_pc2_unpack": [P, P, P, I, I, I, P, P, I, F, P, I, P, P, P, P],
     "tca_pc2_blocks_per_frame": [I],

@@ -5,8 +5,8 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_framework_flags, add_range_flags, add_reference_flags, add_track_flags, bev_view,
-                     labels_arg, load_params, range_options, setup_logging, track_options)
+from .common import (DATA, add_depth_flags, add_framework_flags, add_range_flags, add_reference_flags, add_track_flags,
+                     bev_view, depth_options, labels_arg, load_params, range_options, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -29,8 +29,14 @@ def parse_args(argv=None):
     add_range_flags(p, "write, per cloud, the nearest camera Detection2DArray of --camera-detections-topic (read from "
                        "the bag in a first pass) to the output bag on this topic, with each detection's "
                        "camera-frame position from the LiDAR points (needs --calib)")
+    add_depth_flags(p, "write every cloud as a depth Image registered to the camera's pixels to the output bag on this "
+                       "topic (needs --calib and --depth-size)")
+    p.add_argument("--depth-out", default="", metavar="DIR",
+                   help="save every cloud's 16UC1 depth image as the 16-bit greyscale DIR/NNNN.png (the numbering of "
+                        "--bev-out)")
     flags = p.parse_args(argv)
     flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
+    flags.calibration, flags.depth_options = depth_options(flags, p.error)
     return flags
 
 
@@ -59,7 +65,9 @@ def main(argv=None) -> int:
                          track_options=track_options(flags), ranged_topic=flags.ranged_topic or None,
                          camera_detections_topic=flags.camera_detections_topic or None,
                          calibration=flags.calibration, range_options=flags.range_options,
-                         range_slop=flags.range_slop)
+                         range_slop=flags.range_slop, depth_topic=flags.depth_topic or None,
+                         depth_options=flags.depth_options, depth_frame_id=flags.depth_frame_id or "",
+                         depth_out=flags.depth_out or None)
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

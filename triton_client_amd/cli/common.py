@@ -246,6 +246,71 @@ def range_options(flags, error=None):
     return cal, opts
 
 
+_DEPTH_FLAGS = ("depth_size", "depth_encoding", "depth_scale", "depth_min", "depth_splat", "depth_frame_id")
+
+
+def add_depth_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--depth-topic, --depth-size and --depth-* (``ops/depth_image.py``); --calib is the range
+    flags' own.  The option flags default to None so that one given without a topic is seen."""
+    p.add_argument("--depth-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--depth-size", default=None, metavar="WxH", help="the camera's image size in pixels, e.g. 1280x720")
+    p.add_argument("--depth-encoding", default=None, choices=["16UC1", "32FC1"],
+                   help="16UC1 (default): depth in 1/--depth-scale metres, 0 for no return (REP 118); 32FC1: metres, "
+                        "NaN for no return")
+    p.add_argument("--depth-scale", type=float, default=None, metavar="S",
+                   help="16UC1 units per metre (default 1000: millimetres; 256: the KITTI depth-PNG convention)")
+    p.add_argument("--depth-min", type=float, default=None, metavar="M",
+                   help="points nearer than this many metres in front of the camera are left out (default 0.5)")
+    p.add_argument("--depth-splat", type=int, default=None, metavar="R",
+                   help="a point covers the (2R+1)^2 pixels around its own, 0..4 (default 1)")
+    p.add_argument("--depth-frame-id", default=None, metavar="FRAME",
+                   help="frame_id of the depth images (default: the cloud's)")
+
+
+def depth_options(flags, error=None):
+    """``(calibration, depth_options)`` of the --depth-* flags: ``flags.calibration`` (loaded
+    from --calib when ranging has not) and a ``DepthOptions``, or ``(flags.calibration, None)``
+    without --depth-topic / --depth-out.  A depth topic without --calib or --depth-size, a
+    --depth-* flag without a topic, --depth-out with 32FC1 and an option out of range are usage
+    errors: ``error`` (an ``ArgumentParser.error``) is called with the message, else
+    ``ValueError`` is raised."""
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    cal = getattr(flags, "calibration", None)
+    out_dir = getattr(flags, "depth_out", "")
+    if not (flags.depth_topic or out_dir):
+        given = [f for f in _DEPTH_FLAGS if getattr(flags, f) is not None]
+        if given:
+            fail(f"--{given[0].replace('_', '-')} needs --depth-topic TOPIC" + (" or --depth-out DIR" if hasattr(
+                flags, "depth_out") else ""))
+        return cal, None
+    from ..ops.depth_image import DepthOptions
+    from ..ops.range2d import load_calibration
+
+    what = "--depth-topic" if flags.depth_topic else "--depth-out"
+    if not flags.calib:
+        fail(f"{what} needs --calib FILE")
+    if not flags.depth_size:
+        fail(f"{what} needs --depth-size WxH")
+    try:
+        w, h = (int(v) for v in flags.depth_size.lower().split("x"))
+    except ValueError:
+        fail(f"--depth-size: want WxH, e.g. 1280x720, got {flags.depth_size!r}")
+    if out_dir and flags.depth_encoding == "32FC1":
+        fail("--depth-out writes 16-bit PNGs: it needs --depth-encoding 16UC1")
+    kw = {k: v for k, v in (("encoding", flags.depth_encoding), ("scale", flags.depth_scale),
+                            ("min_depth", flags.depth_min), ("splat", flags.depth_splat)) if v is not None}
+    try:
+        opts = DepthOptions(width=w, height=h, **kw)
+        cal = cal if cal is not None else load_calibration(flags.calib)
+    except (ValueError, OSError) as e:
+        fail(f"{what}: {e}")
+    return cal, opts
+
+
 def bev_view(engine, res: float, enabled):
     """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
     range for an engine that does not know its model's) at ``res`` metres per pixel; None

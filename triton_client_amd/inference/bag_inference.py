@@ -112,10 +112,19 @@ def _save_png(path, im) -> None:
     PILImage.fromarray(decode_image_msg(im)).save(path)
 
 
+def _save_depth_png(path, im) -> None:
+    """A ``16UC1`` Image as a 16-bit greyscale PNG (the KITTI depth-PNG container)."""
+    import numpy as np
+    from PIL import Image as PILImage
+
+    a = np.frombuffer(im.data, "<u2").reshape(im.height, im.width)
+    PILImage.fromarray(a.astype(np.uint16)).save(path)
+
+
 class BagInference3D(RosInference3D):
     def __init__(self, channel=None, client=None, bagfile: str = "", out_bag: Optional[str] = "", batch: int = 8,
                  start_seq: int = 0, max_frames: Optional[int] = None, verbose: bool = False,
-                 bev_out: Optional[str] = None, **kw):
+                 bev_out: Optional[str] = None, depth_out: Optional[str] = None, **kw):
         """bev_out: a directory; every cloud's bird's-eye-view picture is saved there as
         ``NNNN.png`` (the naming of the 2D replay's ``out_dir``) and, with an output bag,
         written to it on ``bev_topic`` (default ``<pub_topic>/bev``).  With ``points_topic`` the
@@ -123,8 +132,15 @@ class BagInference3D(RosInference3D):
         ``tracks_topic`` the tracks message (the clouds are tracked in bag order).  With
         ``ranged_topic`` the bag's ``camera_detections_topic`` is read in a first pass, so the
         pairing is deterministic, and the ranged message of every cloud that has a partner is
-        written on that topic."""
+        written on that topic.  With ``depth_topic`` every cloud's depth image is written on that
+        topic; ``depth_out``: a directory where it is also saved as a 16-bit greyscale
+        ``NNNN.png`` (``16UC1`` only; the topic defaults to ``<pub_topic>/depth``)."""
+        if depth_out and not kw.get("depth_topic"):
+            kw["depth_topic"] = ((kw.get("params") or {}).get("pub_topic") or "") + "/depth"
         super().__init__(channel, client, **kw)
+        self.depth_out = depth_out or None
+        if self.depth_out and self.depth_options.encoding != "16UC1":
+            raise ValueError("depth_out writes 16-bit PNGs: it needs the 16UC1 encoding")
         self.bev_out = bev_out or None
         if self.bev_out and not self.bev_topic:
             self.enable_bev(self.params["pub_topic"] + "/bev", kw.get("bev_view"))
@@ -138,6 +154,8 @@ class BagInference3D(RosInference3D):
         p = self.params
         if self.bev_out:
             os.makedirs(self.bev_out, exist_ok=True)
+        if self.depth_out:
+            os.makedirs(self.depth_out, exist_ok=True)
         ob = Bag(self.out_bag, "w") if self.out_bag else None
         count = 0
         t0 = time.perf_counter()
@@ -175,6 +193,10 @@ class BagInference3D(RosInference3D):
                             ob.write(self.tracks_topic, pic[2])
                         if self.ranged_topic and pred.get("ranged") is not None:
                             ob.write(self.ranged_topic, pred["ranged"])
+                        if self.depth_topic:
+                            ob.write(self.depth_topic, pred["depth"])
+                    if self.depth_out:
+                        _save_depth_png(os.path.join(self.depth_out, f"{count:04}.png"), pred["depth"])
                     if self.verbose:
                         print(m.header.seq)
                     self.results.append((m.header.seq, pred))

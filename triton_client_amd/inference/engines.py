@@ -215,6 +215,23 @@ class Detector3D(ABC):
             out[b] = r2.ranged_message(detection_msgs[b], cam, ok)
         return out
 
+    def depth_imager(self):
+        """This engine's :class:`~triton_client_amd.ops.depth_image.DepthImager`, made once like
+        :meth:`ranger` (``tca_depth_image`` on the engine's GPU, else the host definition)."""
+        from ..ops.depth_image import DepthImager
+
+        return Detector3D._made_once(self, "_depth_imager", DepthImager)
+
+    def depth_images(self, clouds: Sequence[msgs.PointCloud2], calibration, opts, frame_id: str = "") -> List[msgs.Image]:
+        """Each cloud seen from the camera: per cloud one ``Image`` of depths (``opts``: a
+        :class:`~triton_client_amd.ops.depth_image.DepthOptions`) with the cloud's stamp, in
+        frame ``frame_id`` (the cloud's when empty).  Points are the message's own x, y, z:
+        ``calibration.T`` starts in the sensor frame."""
+        from ..ops import depth_image as di
+
+        pics = Detector3D.depth_imager(self).images(clouds, calibration.M, opts)  # (duck-typed too)
+        return [di.depth_message(c, im, opts, frame_id) for c, im in zip(clouds, pics)]
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

@@ -45,6 +45,14 @@ id 0 and score 0.  Live pairing is best effort: a camera message that arrives af
 cloud was processed is missed (bag replay reads the camera topic first and misses none).
 The message rides in the prediction as ``pred["ranged"]``; every other message keeps its
 bytes, and with the option off nothing changes.
+
+``depth_topic`` (with ``calibration`` — the one ranging uses — and ``depth_options``, a
+``DepthOptions`` or a dict of its fields): the driver also publishes, per cloud, the cloud seen
+from the camera (``ops/depth_image.py``: ``tca_depth_image`` on an engine's GPU): an ``Image``
+of ``depth_options.encoding`` (REP 118 ``16UC1``, or ``32FC1``) registered to the camera's
+pixels, with the cloud's stamp and seq, in frame ``depth_frame_id`` (the cloud's when empty).
+It is published after the box message of the same cloud, in published order, and rides in the
+prediction as ``pred["depth"]``; every other message keeps its bytes.
 """
 from __future__ import annotations
 
@@ -126,7 +134,8 @@ class RosInference3D(BaseInference):
                  bev_view=None, points_topic: Optional[str] = None, tracks_topic: Optional[str] = None,
                  track_options: Optional[dict] = None, ranged_topic: Optional[str] = None,
                  camera_detections_topic: Optional[str] = None, calibration=None,
-                 range_options: Optional[dict] = None, range_slop: float = 0.05):
+                 range_options: Optional[dict] = None, range_slop: float = 0.05, depth_topic: Optional[str] = None,
+                 depth_options=None, depth_frame_id: str = ""):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -148,6 +157,15 @@ class RosInference3D(BaseInference):
             RangeOptions(**self.range_options)  # a bad option fails here, not in the first batch
             # holds a camera message for as long as its cloud may wait in the driver's window
             self.pairer = StampPairer(max(64, queue_size or 0, 2 * max(1, batch) * max(1, workers)))
+        self.depth_topic, self.depth_pub, self.depth_frame_id = depth_topic or None, None, depth_frame_id or ""
+        self.depth_options = depth_options
+        if self.depth_topic:
+            from ..ops.depth_image import DepthOptions
+
+            if calibration is None or depth_options is None:
+                raise ValueError("depth_topic needs calibration and depth_options")
+            if not isinstance(depth_options, DepthOptions):
+                self.depth_options = DepthOptions(**depth_options)  # a bad option fails here
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
@@ -172,6 +190,8 @@ class RosInference3D(BaseInference):
             self.ranged_pub = compat.Publisher(self.ranged_topic, msgs.Detection2DArray, queue_size=1, bus=self.bus)
             self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
                                                 self.pairer.push, queue_size=None, bus=self.bus)
+        if self.depth_topic:
+            self.depth_pub = compat.Publisher(self.depth_topic, msgs.Image, queue_size=1, bus=self.bus)
         cb, qs = self._pc_callback, self.queue_size
         if self.batch > 1 or self.workers > 1:
             from .batching import MicroBatchRunner
@@ -212,10 +232,13 @@ class RosInference3D(BaseInference):
     def _item(r: tuple) -> tuple:
         """What is published of one ``process`` (or :meth:`track`) result: (box message, picture or
         None[, labelled cloud or None[, tracks message]]); a prediction that was ranged makes it
-        five long: (..., tracks message or None, ranged message or None)."""
+        five long: (..., tracks message or None, ranged message or None), one with a depth image
+        six: (..., ranged message or None, depth Image)."""
         item = (r[0],) + (tuple(r[2:]) if len(r) > 2 else (None,))
         if isinstance(r[1], dict) and "ranged" in r[1]:
             item = item + (None,) * (4 - len(item)) + (r[1]["ranged"],)
+        if isinstance(r[1], dict) and "depth" in r[1]:
+            item = item + (None,) * (5 - len(item)) + (r[1]["depth"],)
         return item
 
     def _publish(self, item) -> None:
@@ -229,6 +252,8 @@ class RosInference3D(BaseInference):
             self.tracks_pub.publish(item[3])
         if len(item) > 4 and item[4] is not None and self.ranged_pub is not None:
             self.ranged_pub.publish(item[4])
+        if len(item) > 5 and item[5] is not None and self.depth_pub is not None:
+            self.depth_pub.publish(item[5])
 
     def to_msg(self, pred: dict, header: msgs.Header):
         idx = select_boxes(pred, self.labels, self.score_thresh)
@@ -270,6 +295,9 @@ class RosInference3D(BaseInference):
         if self.ranged_topic:
             with timer("range2d"):
                 self._range(clouds, preds)
+        if self.depth_topic:
+            with timer("depth_image"):
+                self._depth(clouds, preds)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -296,6 +324,14 @@ class RosInference3D(BaseInference):
             Detector3D.range_detections(self.engine, clouds, partners, self.calibration, **self.range_options)
         for p, m in zip(preds, res):
             p["ranged"] = m
+
+    def _depth(self, clouds, preds) -> None:
+        """``pred["depth"]`` of every cloud: its depth image message.  One call per batch."""
+        fn = getattr(self.engine, "depth_images", None)  # (an engine that is no Detector3D subclass)
+        args = (clouds, self.calibration, self.depth_options, self.depth_frame_id)
+        res = fn(*args) if fn is not None else Detector3D.depth_images(self.engine, *args)
+        for p, m in zip(preds, res):
+            p["depth"] = m
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""

@@ -1,6 +1,6 @@
 """What the ops that read raw ``PointCloud2`` payloads in place share on the host — the point
 labeler (``ops/points_in_boxes.py``, K22), the bird's-eye-view painter (``ops/bev.py``, K23) and
-the camera ranger (``ops/range2d.py``, K26): where a cloud's fields lie (:class:`CloudLayout`),
+the camera ranger (``ops/range2d.py``, K26), the depth imager (``ops/depth_image.py``, K27): where a cloud's fields lie (:class:`CloudLayout`),
 which of them a kernel can read in place (:func:`fields_f32`), the byte layout of one staged
 batch (:func:`plan_staging`, :func:`fill_staging`: no torch in either), and the device side of
 such an op (:class:`CloudStager`).
@@ -144,7 +144,8 @@ class CloudStager:
     batch of same-layout clouds one H2D copy (:meth:`_stage`), the subclass's launch, one D2H copy
     and one synchronize (:meth:`_fetch`), all on that stream; :meth:`_per_cloud` sends each cloud
     to the device or to the definition.  A batch is cut into several launches (:meth:`_parts`)
-    by ``CameraRanger`` alone: ``tca_range2d`` refuses more than 64 frames or 2^31 record bytes,
+    by ``CameraRanger`` and ``DepthImager`` (``ops/depth_image.py``, K27, whose cut also bounds the
+    key plane): ``tca_range2d`` and ``tca_depth_image`` refuse more than 64 frames or 2^31 record bytes,
     while ``tca_points_in_boxes`` checks neither (64-bit frame offsets; its int32 point offsets are
     refused in ``prepare``) and ``tca_bev_render`` takes 65535 frames and a 64-bit byte count."""
 
@@ -210,13 +211,14 @@ class CloudStager:
 
     def _per_cloud(self, clouds: Sequence, takes: Callable, on_host: Callable, group_args: Callable,
                    on_device: Callable, warning: Callable, device: Optional[bool] = None,
-                   host_layouts: bool = True) -> list:
+                   host_layouts: bool = True, parts: Optional[Callable] = None) -> list:
         """One result per cloud, in input order.  With ``device`` (default: ``self.gpu``), cloud
         ``i`` of layout ``lay`` goes to the device when ``takes(i, lay)``: for clouds ``part``, all
         of one layout, ``on_device(*group_args(lay, part))`` returns their results; it alone runs
         under the lock.  Every other cloud is ``on_host(i, lay)``, with one ``warning(i, lay)`` in
         this object's life if there is a device.  ``host_layouts`` False: no layout is computed
-        without a device."""
+        without a device.  ``parts``: cuts a layout's clouds into launches in place of
+        :meth:`_parts` (a cut that depends on the call's options)."""
         device = self.gpu if device is None else device
         lays = [cloud_layout(c) for c in clouds] if device or host_layouts else [None] * len(clouds)
         out: List[Optional[object]] = [None] * len(clouds)
@@ -230,7 +232,7 @@ class CloudStager:
                 warnings.warn(warning(i, lay), RuntimeWarning, stacklevel=3)
             out[i] = on_host(i, lay)
         for lay, idx in groups.items():
-            for part in self._parts(idx, clouds):
+            for part in (parts or self._parts)(idx, clouds):
                 args = group_args(lay, part)
                 with self._lock:
                     res = on_device(*args)

@@ -256,18 +256,25 @@ def _reduce(inside: np.ndarray, bins: np.ndarray, fx: np.ndarray, pct: int, min_
     return n, m, c, sums
 
 
-def project_numpy(points, M, bin_w: float = 0.25, min_depth: float = 0.5):
-    """The per-point part of the definition → ``(u, v, visible, bin)``."""
+def project_uvw(points, M):
+    """``(u, v, w)`` of every point, float32 in the definition's operation order (shared with
+    ``ops/depth_image.py``)."""
     x, y, z = _xyz(points)
     M = np.asarray(M, np.float32).reshape(3, 4)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         w = ((M[2, 0] * x + M[2, 1] * y) + M[2, 2] * z) + M[2, 3]
         a = ((M[0, 0] * x + M[0, 1] * y) + M[0, 2] * z) + M[0, 3]
         b = ((M[1, 0] * x + M[1, 1] * y) + M[1, 2] * z) + M[1, 3]
+        return a / w, b / w, w
+
+
+def project_numpy(points, M, bin_w: float = 0.25, min_depth: float = 0.5):
+    """The per-point part of the definition → ``(u, v, visible, bin)``."""
+    u, v, w = project_uvw(points, M)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         q = w / np.float32(bin_w)
         visible = (w >= np.float32(min_depth)) & (q >= np.float32(0)) & (q < np.float32(NB))
         bins = np.where(visible, q, np.float32(0)).astype(np.int32)
-        u, v = a / w, b / w
     return u, v, visible, bins
 
 
