@@ -280,7 +280,7 @@ def test_driver_publishes_the_definition_and_keeps_every_other_byte(batch, worke
                              workers=workers, queue_size=64, bev_topic="/bev", points_topic="/pts",
                              tracks_topic="/trk" if tracks else None, **kw)
         drv.start_inference(spin=False)
-        for name, p in (("box", drv.pub), ("depth", drv.depth_pub)):  # the order the driver publishes in
+        for name, p in (("box", drv.pub), ("depth", drv.side_pubs.get("depth"))):  # the order the driver publishes in
             if p is not None:
                 def publish(m, name=name, send=p.publish):
                     order.append((name, m.header.seq))
@@ -304,7 +304,7 @@ def test_driver_publishes_the_definition_and_keeps_every_other_byte(batch, worke
     # after the box message of the same cloud, in published order
     assert order == [(k, s) for s in (1, 2, 3, 4) for k in ("box", "depth")]
     seen0, got0, _, drv0 = drive(False)
-    assert got0 == [] and drv0.depth_pub is None and not hasattr(drv0.engine, "_depth_imager")
+    assert got0 == [] and "depth" not in drv0.side_pubs and not hasattr(drv0.engine, "_depth_imager")
     assert seen1 == seen0 and len(seen1["/o"]) == len(seen1["/bev"]) == len(seen1["/pts"]) == 4
     assert len(seen1["/trk"]) == (4 if tracks else 0)
     assert drv1.engine._depth_imager.gpu is False
@@ -318,20 +318,21 @@ def test_process_shapes_and_constructor_refusals():
                          depth_options={"width": 64, "height": 48, "encoding": "32FC1", "splat": 0})
     assert drv.depth_options == D.DepthOptions(64, 48, encoding="32FC1", splat=0)
     res = drv.process(clouds)
-    assert all(len(r) == 2 for r in res)  # the tuple is as before; the message rides in the prediction
     for r, c in zip(res, clouds):
-        assert bytes(r[1]["depth"].data) == _expected(c, drv.depth_options) and r[1]["depth"].header.frame_id == "os"
-    item = drv._item(res[0])
-    assert len(item) == 6 and item[5] is res[0][1]["depth"] and item[1:5] == (None, None, None, None)
+        d = r.pred["depth"]  # the message rides in the prediction too
+        assert bytes(d.data) == _expected(c, drv.depth_options) and d.header.frame_id == "os"
+        assert r.depth is d and (r.bev, r.points, r.tracks, r.ranged) == (None, None, None, None)
+        assert "ranged" not in r.pred
     # with ranging too, one calibration serves both
     both = RosInference3D(engine=_Engine(), params={}, depth_topic="/d", calibration=CAL, depth_options=OPTS,
                           ranged_topic="/r", camera_detections_topic="/c")
     for m in cams:
         both.pairer.push(m)
     r = both.process(clouds)[0]
-    assert len(both._item(r)) == 6 and both._item(r)[4] is r[1]["ranged"] and both._item(r)[5] is r[1]["depth"]
+    assert r.ranged is r.pred["ranged"] is not None and r.depth is r.pred["depth"] is not None
+    assert (r.bev, r.points, r.tracks) == (None, None, None)
     off = RosInference3D(engine=_Engine(), params={})
-    assert all("depth" not in r[1] for r in off.process(clouds))
+    assert all("depth" not in r.pred and r.depth is None for r in off.process(clouds))
     with pytest.raises(ValueError, match="calibration"):
         RosInference3D(engine=_Engine(), params={}, depth_topic="/d", depth_options=OPTS)
     with pytest.raises(ValueError, match="depth_options"):

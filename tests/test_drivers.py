@@ -180,7 +180,7 @@ def test_ros_inference3d_and_bag(tmp_path, server):
     assert len(got) == 1 and isinstance(got[0], msgs.BoundingBoxArray) and got[0].header.seq == 2
     assert len(got[0].boxes) == SMALL_PP.nms_post_max
     # default reference filter (Pedestrian, score > 0.5) on random weights publishes nothing
-    assert len(RosInference3D(ch, Pointpillars_client()).process([_cloud(2)])[0][0].boxes) == 0
+    assert len(RosInference3D(ch, Pointpillars_client()).process([_cloud(2)])[0].boxes.boxes) == 0
 
     bag = str(tmp_path / "pc.bag")
     with Bag(bag, "w") as b:

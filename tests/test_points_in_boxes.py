@@ -260,8 +260,9 @@ def test_process_tuple_and_layout_fallbacks():
     clouds = _clouds(2)
     drv = RosInference3D(engine=_Engine(), params={"sub_topic": "/pc", "pub_topic": "/o"}, points_topic="/p")
     r = drv.process(clouds)[0]
-    assert len(r) == 4 and r[2] is None and isinstance(r[3], msgs.PointCloud2)
-    assert len(RosInference3D(engine=_Engine(), params={}).process(clouds)[0]) == 2
+    assert r.bev is None and isinstance(r.points, msgs.PointCloud2) and r.tracks is None
+    plain = RosInference3D(engine=_Engine(), params={}).process(clouds)[0]
+    assert (plain.bev, plain.points, plain.tracks, plain.ranged, plain.depth) == (None,) * 5
     # a FLOAT64 cloud without intensity: values cast to float32, intensity 0
     p = pib.cloud_xyzi(clouds[0])[:, :3].astype(np.float64)
     c64 = msgs.PointCloud2(header=msgs.Header(seq=9), height=1, width=len(p),

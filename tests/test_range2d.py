@@ -374,13 +374,14 @@ def test_process_shapes_and_options():
     for m in cams:
         drv.pairer.push(m)
     res = drv.process(clouds)
-    assert all(len(r) == 2 for r in res)  # the tuple is as before; the message rides in the prediction
-    assert [r[1]["ranged"] is not None for r in res] == [True, True, False, True]
-    assert all(d.results[0].pose.position == msgs.Point() for d in res[0][1]["ranged"].detections)  # min_points
-    assert len(drv._item(res[0])) == 5 and drv._item(res[0])[4] is res[0][1]["ranged"]
+    # no other side output; the message rides in the prediction too
+    assert all((r.bev, r.points, r.tracks, r.depth) == (None,) * 4 for r in res)
+    assert [r.pred["ranged"] is not None for r in res] == [True, True, False, True]
+    assert all(d.results[0].pose.position == msgs.Point() for d in res[0].pred["ranged"].detections)  # min_points
+    assert all(r.ranged is r.pred["ranged"] for r in res)
     off = RosInference3D(engine=_Engine(), params={})
     r0 = off.process(clouds)
-    assert all(len(r) == 2 and "ranged" not in r[1] for r in r0) and len(off._item(r0[0])) == 2
+    assert all((r.bev, r.points, r.tracks, r.ranged, r.depth) == (None,) * 5 and "ranged" not in r.pred for r in r0)
     assert drv.engine._ranger.gpu is False
     with pytest.raises(ValueError, match="calibration"):
         RosInference3D(engine=_Engine(), params={}, ranged_topic="/r", camera_detections_topic="/c")

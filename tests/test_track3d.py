@@ -308,7 +308,7 @@ def _drive(clouds, tracks, jsk=True, batch=1, workers=1, slow=False):
             return r
         drv.process = slow_process
     track = drv.track
-    drv.track = lambda rs: (seen.extend((r[0].header.seq, r[0].header.frame_id) for r in rs), track(rs))[1]
+    drv.track = lambda rs: (seen.extend((r.boxes.header.seq, r.boxes.header.frame_id) for r in rs), track(rs))[1]
     drv.start_inference(spin=False)
     pub = compat.Publisher("/pc", msgs.PointCloud2, bus=bus)
     for c in clouds:
@@ -347,20 +347,22 @@ def test_tracked_predictions_and_ids_over_the_run():
     res = drv.track(drv.process(clouds))
     by_place = {}
     for c, r in zip(clouds, res):
-        assert len(r) == 5 and r[2] is None and r[3] is None and isinstance(r[4], msgs.BoundingBoxArray)
-        pred = r[1]
-        assert r[4].header.seq == c.header.seq and r[4].header.stamp == c.header.stamp
-        assert len(pred["track_ids"]) == len(pred["track_hits"]) == len(pred["track_vel"]) == len(r[0].boxes)
-        assert [b.label for b in r[4].boxes] == pred["track_ids"].tolist()
-        assert [b.label for b in r[0].boxes] == [2] * len(r[0].boxes)
-        for b0, b1 in zip(r[0].boxes, r[4].boxes):
+        assert r.bev is None and r.points is None and isinstance(r.tracks, msgs.BoundingBoxArray)
+        assert r.ranged is None and r.depth is None
+        pred = r.pred
+        assert r.tracks.header.seq == c.header.seq and r.tracks.header.stamp == c.header.stamp
+        assert len(pred["track_ids"]) == len(pred["track_hits"]) == len(pred["track_vel"]) == len(r.boxes.boxes)
+        assert [b.label for b in r.tracks.boxes] == pred["track_ids"].tolist()
+        assert [b.label for b in r.boxes.boxes] == [2] * len(r.boxes.boxes)
+        for b0, b1 in zip(r.boxes.boxes, r.tracks.boxes):
             assert b0.pose == b1.pose and b0.dimensions == b1.dimensions and b0.value == b1.value
         for (x, y), i in zip(pred["pred_boxes"][:, :2], pred["track_ids"]):
             key = "a" if y == 0.0 else "b" if y == 1.0 else "c"
             by_place.setdefault(key, set()).add(int(i))
     assert by_place == {"a": {1}, "b": {2}, "c": {3}} or sorted(map(sorted, by_place.values())) == [[1], [2], [3]]
     assert drv.tracker().kind == "host definition" and drv.tracker().frames == 8
-    assert len(RosInference3D(engine=_Engine(), params={}).process(clouds)[0]) == 2  # process() is as before
+    plain = RosInference3D(engine=_Engine(), params={}).process(clouds)[0]  # process() is as before
+    assert (plain.bev, plain.points, plain.tracks, plain.ranged, plain.depth) == (None,) * 5
 
 
 def test_ordered_stage_of_the_republisher():

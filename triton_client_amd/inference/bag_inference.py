@@ -21,7 +21,7 @@ from typing import Optional
 
 from ..ros.bag import Bag
 from .ros_inference import RosInference
-from .ros_inference3d import RosInference3D
+from .ros_inference3d import SIDE_OUTPUTS, RosInference3D
 
 
 def _ingest(engine):
@@ -178,28 +178,20 @@ class BagInference3D(RosInference3D):
                 res = self.process(chunk)
                 if self.tracks_topic:
                     res = self.track(res)
-                for m, (out, pred, *pic) in zip(chunk, res):
-                    bev = pic[0] if pic else None
-                    if bev is not None and self.bev_out:
-                        _save_png(os.path.join(self.bev_out, f"{count:04}.png"), bev)
+                for m, r in zip(chunk, res):
+                    if r.bev is not None and self.bev_out:
+                        _save_png(os.path.join(self.bev_out, f"{count:04}.png"), r.bev)
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
-                        ob.write(p["pub_topic"], out)
-                        if bev is not None:
-                            ob.write(self.bev_topic, bev)
-                        if len(pic) > 1 and pic[1] is not None:
-                            ob.write(self.points_topic, pic[1])
-                        if len(pic) > 2:
-                            ob.write(self.tracks_topic, pic[2])
-                        if self.ranged_topic and pred.get("ranged") is not None:
-                            ob.write(self.ranged_topic, pred["ranged"])
-                        if self.depth_topic:
-                            ob.write(self.depth_topic, pred["depth"])
+                        ob.write(p["pub_topic"], r.boxes)
+                        for name, _ in SIDE_OUTPUTS:
+                            if getattr(r, name) is not None:
+                                ob.write(self.side_topic(name), getattr(r, name))
                     if self.depth_out:
-                        _save_depth_png(os.path.join(self.depth_out, f"{count:04}.png"), pred["depth"])
+                        _save_depth_png(os.path.join(self.depth_out, f"{count:04}.png"), r.depth)
                     if self.verbose:
                         print(m.header.seq)
-                    self.results.append((m.header.seq, pred))
+                    self.results.append((m.header.seq, r.pred))
                     count += 1
         self.elapsed = time.perf_counter() - t0
         if ob is not None:

@@ -53,9 +53,15 @@ of ``depth_options.encoding`` (REP 118 ``16UC1``, or ``32FC1``) registered to th
 pixels, with the cloud's stamp and seq, in frame ``depth_frame_id`` (the cloud's when empty).
 It is published after the box message of the same cloud, in published order, and rides in the
 prediction as ``pred["depth"]``; every other message keeps its bytes.
+
+Whatever is on, one cloud makes one :class:`CloudResult`: the box message, the prediction and
+one field per option above, None where the option is off (or, for ``ranged``, where the cloud
+found no partner).  :data:`SIDE_OUTPUTS` names those fields in the order they are published
+in, after the box message.
 """
 from __future__ import annotations
 
+import dataclasses
 import time
 from typing import List, Optional, Sequence
 
@@ -126,6 +132,25 @@ def boxes_to_detection3d(pred: dict, idx, header: msgs.Header, ids=None) -> msgs
     return arr
 
 
+@dataclasses.dataclass
+class CloudResult:
+    """What the driver made of one cloud.  ``ranged`` and ``depth`` are the objects that also
+    ride in ``pred`` under those keys."""
+    boxes: object  # BoundingBoxArray, or Detection3DArray
+    pred: dict
+    bev: Optional[msgs.Image] = None
+    points: Optional[msgs.PointCloud2] = None
+    tracks: object = None  # a message of the box message's type
+    ranged: Optional[msgs.Detection2DArray] = None
+    depth: Optional[msgs.Image] = None
+
+
+# The side outputs in publishing order: (CloudResult field, message type; None: the box message's).
+# The driver's ``<name>_topic`` attribute holds the topic, None when the option is off.
+SIDE_OUTPUTS = (("bev", msgs.Image), ("points", msgs.PointCloud2), ("tracks", None),
+                ("ranged", msgs.Detection2DArray), ("depth", msgs.Image))
+
+
 class RosInference3D(BaseInference):
     def __init__(self, channel=None, client=None, engine: Optional[Detector3D] = None, params: Optional[dict] = None,
                  bus=None, jsk: bool = True, labels: Optional[Sequence[int]] = (2,), score_thresh: float = 0.5,
@@ -139,13 +164,12 @@ class RosInference3D(BaseInference):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
-        self.bev_topic, self.bev_view, self.bev_pub = None, None, None
+        self.bev_topic, self.bev_view = None, None
         if bev_topic:
             self.enable_bev(bev_topic, bev_view)
-        self.points_topic, self.points_pub = points_topic or None, None
-        self.tracks_topic, self.tracks_pub = tracks_topic or None, None
+        self.points_topic, self.tracks_topic = points_topic or None, tracks_topic or None
         self.track_options = dict(track_options or {})
-        self.ranged_topic, self.ranged_pub, self.camera_sub = ranged_topic or None, None, None
+        self.ranged_topic, self.camera_sub = ranged_topic or None, None
         self.camera_detections_topic, self.calibration = camera_detections_topic or None, calibration
         self.range_options, self.range_slop = dict(range_options or {}), float(range_slop)
         self.pairer = None
@@ -157,7 +181,7 @@ class RosInference3D(BaseInference):
             RangeOptions(**self.range_options)  # a bad option fails here, not in the first batch
             # holds a camera message for as long as its cloud may wait in the driver's window
             self.pairer = StampPairer(max(64, queue_size or 0, 2 * max(1, batch) * max(1, workers)))
-        self.depth_topic, self.depth_pub, self.depth_frame_id = depth_topic or None, None, depth_frame_id or ""
+        self.depth_topic, self.depth_frame_id = depth_topic or None, depth_frame_id or ""
         self.depth_options = depth_options
         if self.depth_topic:
             from ..ops.depth_image import DepthOptions
@@ -170,6 +194,7 @@ class RosInference3D(BaseInference):
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
         self.sub = self.pub = None
+        self.side_pubs = {}  # the publishers of the side outputs that are on, by SIDE_OUTPUTS name
         # batch > 1: the reference's queue of 50 becomes a latest-wins window
         # drained as micro-batches (one engine call per batch), re-published in
         # header.seq order (see .batching)
@@ -180,28 +205,18 @@ class RosInference3D(BaseInference):
         p = self.params
         t = msgs.BoundingBoxArray if self.jsk else msgs.Detection3DArray
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
-        if self.bev_topic:
-            self.bev_pub = compat.Publisher(self.bev_topic, msgs.Image, queue_size=1, bus=self.bus)
-        if self.points_topic:
-            self.points_pub = compat.Publisher(self.points_topic, msgs.PointCloud2, queue_size=1, bus=self.bus)
-        if self.tracks_topic:
-            self.tracks_pub = compat.Publisher(self.tracks_topic, t, queue_size=1, bus=self.bus)
+        self.side_pubs = {name: compat.Publisher(self.side_topic(name), mtype or t, queue_size=1, bus=self.bus)
+                          for name, mtype in SIDE_OUTPUTS if self.side_topic(name)}
         if self.ranged_topic:
-            self.ranged_pub = compat.Publisher(self.ranged_topic, msgs.Detection2DArray, queue_size=1, bus=self.bus)
             self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
                                                 self.pairer.push, queue_size=None, bus=self.bus)
-        if self.depth_topic:
-            self.depth_pub = compat.Publisher(self.depth_topic, msgs.Image, queue_size=1, bus=self.bus)
         cb, qs = self._pc_callback, self.queue_size
         if self.batch > 1 or self.workers > 1:
             from .batching import MicroBatchRunner
-            cap = max(self.queue_size or 0, 2 * self.batch * self.workers)
-            if self.tracks_topic:  # the workers hand over whole results; the ordered stage tracks them
-                self.runner = MicroBatchRunner(self.process, lambda r: self._publish(self._item(r)), batch=self.batch,
-                                               workers=self.workers, capacity=cap, ordered_fn=self.track)
-            else:
-                self.runner = MicroBatchRunner(lambda cs: [self._item(r) for r in self.process(cs)], self._publish,
-                                               batch=self.batch, workers=self.workers, capacity=cap)
+            # the workers hand over whole results; the tracker is the stage that sees them in published order
+            self.runner = MicroBatchRunner(self.process, self._publish, batch=self.batch, workers=self.workers,
+                                           capacity=max(self.queue_size or 0, 2 * self.batch * self.workers),
+                                           ordered_fn=self.track if self.tracks_topic else None)
             cb, qs = self.runner.push, None
         self.sub = compat.Subscriber(p["sub_topic"], msgs.PointCloud2, cb, queue_size=qs, bus=self.bus,
                                      ingest=getattr(self.engine, "ingest_buffer", None))
@@ -228,32 +243,24 @@ class RosInference3D(BaseInference):
         self.bev_topic = topic
         self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
 
-    @staticmethod
-    def _item(r: tuple) -> tuple:
-        """What is published of one ``process`` (or :meth:`track`) result: (box message, picture or
-        None[, labelled cloud or None[, tracks message]]); a prediction that was ranged makes it
-        five long: (..., tracks message or None, ranged message or None), one with a depth image
-        six: (..., ranged message or None, depth Image)."""
-        item = (r[0],) + (tuple(r[2:]) if len(r) > 2 else (None,))
-        if isinstance(r[1], dict) and "ranged" in r[1]:
-            item = item + (None,) * (4 - len(item)) + (r[1]["ranged"],)
-        if isinstance(r[1], dict) and "depth" in r[1]:
-            item = item + (None,) * (5 - len(item)) + (r[1]["depth"],)
-        return item
+    def side_topic(self, name: str) -> Optional[str]:
+        """The topic of the side output ``name`` of :data:`SIDE_OUTPUTS`, None when it is off."""
+        return getattr(self, name + "_topic")
 
-    def _publish(self, item) -> None:
-        m, im = item[0], item[1]
-        self.pub.publish(m)
-        if im is not None and self.bev_pub is not None:
-            self.bev_pub.publish(im)
-        if len(item) > 2 and item[2] is not None and self.points_pub is not None:
-            self.points_pub.publish(item[2])
-        if len(item) > 3 and item[3] is not None and self.tracks_pub is not None:
-            self.tracks_pub.publish(item[3])
-        if len(item) > 4 and item[4] is not None and self.ranged_pub is not None:
-            self.ranged_pub.publish(item[4])
-        if len(item) > 5 and item[5] is not None and self.depth_pub is not None:
-            self.depth_pub.publish(item[5])
+    def _engine(self, name: str, *args, **kw):
+        """The engine's own ``name`` method; an engine that is no Detector3D subclass and has none
+        gets ``Detector3D``'s, with itself as ``self``."""
+        fn = getattr(self.engine, name, None)
+        return fn(*args, **kw) if fn is not None else getattr(Detector3D, name)(self.engine, *args, **kw)
+
+    def _publish(self, r: CloudResult) -> None:
+        """One cloud's messages: the box message, then every side output it has, in
+        :data:`SIDE_OUTPUTS` order."""
+        self.pub.publish(r.boxes)
+        for name, _ in SIDE_OUTPUTS:
+            m = getattr(r, name)
+            if m is not None:
+                self.side_pubs[name].publish(m)
 
     def to_msg(self, pred: dict, header: msgs.Header):
         idx = select_boxes(pred, self.labels, self.score_thresh)
@@ -267,10 +274,10 @@ class RosInference3D(BaseInference):
             self._live_exec = fn() if callable(fn) else None
         return self._live_exec
 
-    def process(self, clouds: Sequence[msgs.PointCloud2]) -> List[tuple]:
-        """-> [(box message, prediction)] per cloud; with ``bev_topic``,
-        [(box message, prediction, bird's-eye-view Image)]; with ``points_topic``,
-        [(box message, prediction, bird's-eye-view Image or None, labelled PointCloud2)]."""
+    def process(self, clouds: Sequence[msgs.PointCloud2]) -> List[CloudResult]:
+        """One :class:`CloudResult` per cloud, in order: the box message, the prediction and the
+        side output of every option that is on except ``tracks``, which :meth:`track` fills.  One
+        engine call per stage for the whole batch; safe to call from several workers."""
         t0 = time.perf_counter()
         timer = StageTimer(self.metrics)
         live = self._live()
@@ -279,87 +286,76 @@ class RosInference3D(BaseInference):
             preds = live.process(clouds) if live is not None else self.engine.detect(clouds)
         if view is not None:
             with timer("bev_render"):
-                fn = getattr(self.engine, "render_bev", None)  # (an engine that is no Detector3D subclass)
-                pics = fn(clouds, preds, view) if fn is not None else Detector3D.render_bev(self.engine, clouds,
-                                                                                            preds, view)
+                pics = self._engine("render_bev", clouds, preds, view)
         with timer("boxes_publish"):
-            out = [(self.to_msg(p, c.header), p) for c, p in zip(clouds, preds)]
-            if pics is not None:
-                out = [(m, p, msgs.Image(header=c.header, height=view.H, width=view.W, encoding="rgb8",
-                                         is_bigendian=0, step=3 * view.W,
-                                         data=memoryview(np.ascontiguousarray(f).reshape(-1))))
-                       for (m, p), c, f in zip(out, clouds, pics)]
+            out = [CloudResult(self.to_msg(p, c.header), p) for c, p in zip(clouds, preds)]
+            for r, c, f in zip(out, clouds, pics if pics is not None else ()):
+                r.bev = msgs.Image(header=c.header, height=view.H, width=view.W, encoding="rgb8", is_bigendian=0,
+                                   step=3 * view.W, data=memoryview(np.ascontiguousarray(f).reshape(-1)))
         if self.points_topic:
             with timer("points_label"):
-                out = self._with_points(clouds, preds, out)
+                self._points(clouds, out)
         if self.ranged_topic:
             with timer("range2d"):
-                self._range(clouds, preds)
+                self._range(clouds, out)
         if self.depth_topic:
             with timer("depth_image"):
-                self._depth(clouds, preds)
+                self._depth(clouds, out)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
             self.metrics.frame(len(clouds))
         return out
 
-    def _with_points(self, clouds, preds, out: List[tuple]) -> List[tuple]:
-        """Each result with the labelled cloud as its fourth element: points labelled against the
-        boxes the box message carries, so ``instance`` indexes that message."""
+    def _points(self, clouds, out: List[CloudResult]) -> None:
+        """``points`` of every result: the cloud labelled against the boxes the box message
+        carries, so ``instance`` indexes that message."""
         from ..ops.points_in_boxes import labelled_cloud
 
+        preds = [r.pred for r in out]
         idx = [select_boxes(p, self.labels, self.score_thresh) for p in preds]
-        fn = getattr(self.engine, "label_points", None)  # (an engine that is no Detector3D subclass)
-        res = fn(clouds, preds, idx) if fn is not None else Detector3D.label_points(self.engine, clouds, preds, idx)
-        return [(r[0], r[1], r[2] if len(r) > 2 else None, labelled_cloud(c, payload))
-                for r, c, (_, _, payload) in zip(out, clouds, res)]
+        for r, c, (_, _, payload) in zip(out, clouds, self._engine("label_points", clouds, preds, idx)):
+            r.points = labelled_cloud(c, payload)
 
-    def _range(self, clouds, preds) -> None:
-        """``pred["ranged"]`` of every cloud: its nearest camera message with ranges, None
-        without a partner within the slop.  One ranging call per batch."""
+    def _range(self, clouds, out: List[CloudResult]) -> None:
+        """``ranged`` and ``pred["ranged"]`` of every result: the cloud's nearest camera message
+        with ranges, None without a partner within the slop.  One ranging call per batch."""
         partners = [self.pairer.nearest(c.header.stamp, self.range_slop) for c in clouds]
-        fn = getattr(self.engine, "range_detections", None)  # (an engine that is no Detector3D subclass)
-        res = fn(clouds, partners, self.calibration, **self.range_options) if fn is not None else \
-            Detector3D.range_detections(self.engine, clouds, partners, self.calibration, **self.range_options)
-        for p, m in zip(preds, res):
-            p["ranged"] = m
+        res = self._engine("range_detections", clouds, partners, self.calibration, **self.range_options)
+        for r, m in zip(out, res):
+            r.ranged = r.pred["ranged"] = m
 
-    def _depth(self, clouds, preds) -> None:
-        """``pred["depth"]`` of every cloud: its depth image message.  One call per batch."""
-        fn = getattr(self.engine, "depth_images", None)  # (an engine that is no Detector3D subclass)
-        args = (clouds, self.calibration, self.depth_options, self.depth_frame_id)
-        res = fn(*args) if fn is not None else Detector3D.depth_images(self.engine, *args)
-        for p, m in zip(preds, res):
-            p["depth"] = m
+    def _depth(self, clouds, out: List[CloudResult]) -> None:
+        """``depth`` and ``pred["depth"]`` of every result: the cloud's depth image message.  One
+        call per batch."""
+        res = self._engine("depth_images", clouds, self.calibration, self.depth_options, self.depth_frame_id)
+        for r, m in zip(out, res):
+            r.depth = r.pred["depth"] = m
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""
-        fn = getattr(self.engine, "tracker", None)  # (an engine that is no Detector3D subclass)
-        return fn(**self.track_options) if fn is not None else Detector3D.tracker(self.engine, **self.track_options)
+        return self._engine("tracker", **self.track_options)
 
-    def track(self, results: Sequence[tuple]) -> List[tuple]:
-        """The ordered stage: ``process`` results of consecutive clouds, in published order →
-        each as ``(box message, prediction, picture or None, labelled cloud or None, tracks
-        message)``.  One tracker call per batch; each prediction gains ``track_ids``,
-        ``track_hits`` and ``track_vel``, aligned with the published selection."""
+    def track(self, results: Sequence[CloudResult]) -> List[CloudResult]:
+        """The ordered stage: :meth:`process` results of consecutive clouds, in published order →
+        the same results with ``tracks`` filled.  One tracker call per batch; each prediction
+        gains ``track_ids``, ``track_hits`` and ``track_vel``, aligned with the published
+        selection."""
         results = list(results)
         if not results:
             return []
         timer = StageTimer(self.metrics)
         with timer("track3d"):
-            preds = [r[1] for r in results]
+            preds = [r.pred for r in results]
             idx = [select_boxes(p, self.labels, self.score_thresh) for p in preds]
-            res = self.tracker().track(preds, idx, [r[0].header.stamp for r in results])
-            out = []
+            res = self.tracker().track(preds, idx, [r.boxes.header.stamp for r in results])
             for r, p, ix, (ids, hits, vel) in zip(results, preds, idx, res):
                 p["track_ids"], p["track_hits"], p["track_vel"] = ids, hits, vel
-                h = r[0].header
-                m = boxes_to_jsk(p, ix, h, ids) if self.jsk else boxes_to_detection3d(p, ix, h, ids)
-                out.append((r[0], p, r[2] if len(r) > 2 else None, r[3] if len(r) > 3 else None, m))
-        return out
+                h = r.boxes.header
+                r.tracks = boxes_to_jsk(p, ix, h, ids) if self.jsk else boxes_to_detection3d(p, ix, h, ids)
+        return results
 
     def _pc_callback(self, msg):
         res = self.process([msg])
         for r in (self.track(res) if self.tracks_topic else res):
-            self._publish(self._item(r))
+            self._publish(r)
