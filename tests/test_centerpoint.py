@@ -374,3 +374,25 @@ def test_centerpoint_pipeline_multisweep_graph(cuda):
         assert len(d["pred_scores"]) > 0 and np.isfinite(d["pred_boxes"]).all()
     n0 = int(p.frame_n[0])  # the eager warm-up filled the 2-sweep history: 3 sweeps merged per replay
     assert len(set(counts)) == 1 and 2.5 * n0 < counts[0] <= 3 * n0, (counts, n0)
+
+
+@pytest.mark.gpu
+def test_centerpoint_served_model_gpu(cuda):
+    """The served centerpoint_pp model on the GPU path (PFN from received voxels over the
+    full 512 x 512 canvas): 9-d finite boxes, 0-based nuScenes labels, and the same bytes
+    from a second execute (the canvas cells of a request are cleared before the next)."""
+    from triton_client_amd.server.models import CenterPointModel
+    m = CenterPointModel("centerpoint_pp", device="cuda")
+    m.load()
+    p = lidar_sweep(LidarSpec(rings=32, azimuth_steps=1024, sensor_height=1.8), 7)
+    p = p[~np.isnan(p).any(1)]
+    v, zyx, num, _ = voxelize_np(p, m.cfg.voxel, 4)
+    coords = np.concatenate([np.zeros((len(zyx), 1), np.int32), zyx], 1)
+    req = {"voxels": v, "voxel_coords": coords, "voxel_num_points": num.astype(np.int32)}
+    out = m.execute(req, None)
+    n = len(out["pred_scores"])
+    assert out["pred_boxes"].shape == (n, 9) and n > 0 and np.isfinite(out["pred_boxes"]).all()
+    assert out["pred_labels"].dtype == np.int64 and set(np.unique(out["pred_labels"])) <= set(range(10))
+    out2 = m.execute(req, None)
+    for k in ("pred_boxes", "pred_scores", "pred_labels"):
+        np.testing.assert_array_equal(out[k], out2[k])

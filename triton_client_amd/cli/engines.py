@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import os
 
+from ..config.lidar import lidar_family  # noqa: F401 - the CLIs' name -> family rule lives with the table
 from .common import DATA, make_channel, make_client, resolve_device, rpc_mode
 
 
@@ -70,17 +71,6 @@ def engine_2d(flags, params, letterbox=None, conf_thres=None):
     return eng, ch, client
 
 
-def lidar_family(model_name: str) -> str:
-    """Model family of a served 3D model name (the reference's ``-m`` values:
-    ``second_iou`` by default in .vscode/launch.json, ``pointpillar_kitti``)."""
-    n = model_name.lower()
-    if "second" in n:
-        return "second_iou"
-    if "centerpoint" in n or "nusc" in n:
-        return "centerpoint"
-    return "pointpillars"
-
-
 def engine_3d(flags, params):
     if flags.engine == "local":
         from ..inference import LocalDetector3D
@@ -128,9 +118,9 @@ def maybe_data_parallel(engine, three_d: bool = False):
         from ..parallel.dp import HealthMonitor
 
         monitor = HealthMonitor(info, timeout=float(os.environ.get("TCA_DP_HEARTBEAT_TIMEOUT", "5")))
-    box_dim = 9 if getattr(engine, "family", "") == "centerpoint" else 7
     comm = native_comm(info)
-    wrap = (DataParallelDetector3D(engine, info, box_dim=box_dim, monitor=monitor, comm=comm) if three_d
+    wrap = (DataParallelDetector3D(engine, info, box_dim=getattr(engine, "box_dim", 7), monitor=monitor, comm=comm)
+            if three_d
             else DataParallelDetector2D(engine, info, monitor=monitor, comm=comm))
     return wrap, info
 

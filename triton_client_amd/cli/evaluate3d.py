@@ -40,12 +40,11 @@ def _engine(flags, params):
     """The 3D engine of the flags; a local one scores down to ``--conf-thres``."""
     if flags.engine != "local":
         return engine_3d(flags, params)
-    from ..config import lidar as lc
+    from ..config.lidar import LIDAR_FAMILIES
     from ..inference import LocalDetector3D
 
     family = lidar_family(flags.model_name)
-    cfg = {"pointpillars": lc.PointPillarsConfig, "second_iou": lc.SecondIoUConfig,
-           "centerpoint": lc.CenterPointConfig}[family]()
+    cfg = LIDAR_FAMILIES[family].config()
     cfg = dataclasses.replace(cfg, score_thresh=min(cfg.score_thresh, flags.conf_thres))
     return LocalDetector3D(cfg=cfg, batch=max(1, flags.frames_per_step), device=flags.device, weights=flags.weights,
                            z_offset=flags.z_offset, family=family), None, None

@@ -270,6 +270,66 @@ class CenterPointConfig:
         return ny // self.out_size_factor, nx // self.out_size_factor
 
 
+@dataclass(frozen=True)
+class LidarFamily:
+    """What one LiDAR detector family is, for the served models, the local engine and the
+    CLIs.  ``builder`` and ``pipeline`` are ``"module:name"`` under the package, imported
+    when asked for: this module imports no torch model and no pipeline."""
+    config: type  # the family's config class; config() is its default deployment
+    builder: str  # (cfg, seed) -> the torch module
+    pipeline: str  # the GPU pipeline class
+    calibrate_target: float  # candidates above the score threshold a random-init head is calibrated to
+    z_offset: float  # added to z before voxelising (reference ros_inference3d.py:172), removed from the boxes
+    sweep: Tuple[int, int, float]  # rings, azimuth steps, sensor height (m) of the synthetic calibration sweep
+    box_dim: int  # pred_boxes columns (9: det3d order with vx, vy; yaw last)
+    label_base: int  # the pred_labels value of class_names[0]
+    point_features: int  # columns of the served ``voxels`` input
+
+    def build_model(self, cfg, seed: int):
+        return _resolve(self.builder)(cfg, seed)
+
+    def pipeline_cls(self):
+        return _resolve(self.pipeline)
+
+    def sample_sweep(self, seed: int):
+        """The synthetic sweep a random-init head is calibrated on: [N, 4] float32 x, y, z, intensity."""
+        from ..utils.synthetic import LidarSpec, lidar_sweep
+
+        rings, steps, height = self.sweep
+        return lidar_sweep(LidarSpec(rings=rings, azimuth_steps=steps, sensor_height=height), seed)
+
+
+def _resolve(path: str):
+    import importlib
+
+    mod, _, name = path.partition(":")
+    return getattr(importlib.import_module(".." + mod, __package__), name)
+
+
+LIDAR_FAMILIES = {
+    "pointpillars": LidarFamily(PointPillarsConfig, "models.pointpillars:build_pointpillars",
+                                "pipelines.lidar:LidarPipeline", 2000.0, 1.5, (64, 1875, 3.23), 7, 1, 4),
+    "second_iou": LidarFamily(SecondIoUConfig, "models.second:build_second_iou",
+                              "pipelines.second:SecondPipeline", 60.0, 1.5, (64, 1875, 3.23), 7, 1, 4),
+    "centerpoint": LidarFamily(CenterPointConfig, "models.centerpoint:build_centerpoint",
+                               "pipelines.centerpoint:CenterPointPipeline", 1000.0, 0.0, (32, 1800, 1.8), 9, 0, 5),
+}
+
+
+def lidar_family(model_name: str, default: Optional[str] = "pointpillars") -> Optional[str]:
+    """Family of a served 3D model name (the reference's ``-m`` values: ``second_iou`` by
+    default in .vscode/launch.json, ``pointpillar_kitti``, ``centerpoint_pp``); ``default``
+    for a name of no family."""
+    n = model_name.lower()
+    if "second" in n:
+        return "second_iou"
+    if "centerpoint" in n or "nusc" in n:
+        return "centerpoint"
+    if "pillar" in n:
+        return "pointpillars"
+    return default
+
+
 def anchor_grid(cfg: PointPillarsConfig):
     """Analytic anchor layout (OpenPCDet AnchorGenerator, align_center=False).
 

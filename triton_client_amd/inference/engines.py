@@ -176,7 +176,7 @@ class Detector3D(ABC):
 
             names = list(getattr(self, "names", None) or [])
             md = options.pop("max_dist", None)
-            if getattr(self, "family", None) == "centerpoint" and (md is None or isinstance(md, dict)):
+            if getattr(self, "label_base", 1) == 0 and (md is None or isinstance(md, dict)):  # nuScenes labels
                 have = {n.lower() for n in names}
                 md = {**{k: v for k, v in CENTERPOINT_MAX_DIST.items() if k in have},
                       **{str(k).lower(): v for k, v in (md or {}).items()}}
@@ -476,43 +476,25 @@ class LocalDetector3D(Detector3D):
     On a GPU-less host the same semantics run on the CPU (vectorised
     voxeliser + the fp32 reference modules)."""
 
-    FAMILIES = {"pointpillars": 2000.0, "second_iou": 60.0, "centerpoint": 1000.0}  # default calibration targets
-    Z_OFFSET = {"pointpillars": 1.5, "second_iou": 1.5, "centerpoint": 0.0}
-
     def __init__(self, cfg=None, batch: int = 1, device="auto", graph: bool = True, weights: Optional[str] = None,
                  calibrate_target="auto", z_offset: Optional[float] = None, normalize_intensity: bool = True,
                  seed: int = 0, max_points: int = 131072, family: str = "pointpillars"):
-        if family not in self.FAMILIES:
-            raise ValueError(f"family {family!r}: one of {sorted(self.FAMILIES)}")
-        self.family = family
+        from ..config.lidar import LIDAR_FAMILIES
+
+        if family not in LIDAR_FAMILIES:
+            raise ValueError(f"family {family!r}: one of {sorted(LIDAR_FAMILIES)}")
+        self.family, self.fam = family, LIDAR_FAMILIES[family]
         self.device = _device(device)
-        if family == "pointpillars":
-            from ..config.lidar import PointPillarsConfig
-            from ..models.pointpillars import build_pointpillars
-
-            self.cfg = cfg or PointPillarsConfig()
-            self.model = build_pointpillars(self.cfg, seed)
-        elif family == "second_iou":
-            from ..config.lidar import SecondIoUConfig
-            from ..models.second import build_second_iou
-
-            self.cfg = cfg or SecondIoUConfig()
-            self.model = build_second_iou(self.cfg, seed)
-        else:
-            from ..config.lidar import CenterPointConfig
-            from ..models.centerpoint import build_centerpoint
-
-            self.cfg = cfg or CenterPointConfig()
-            self.model = build_centerpoint(self.cfg, seed)
-        self.box_dim = 9 if family == "centerpoint" else 7
-        self.label_base = 0 if family == "centerpoint" else 1
+        self.cfg = cfg or self.fam.config()
+        self.model = self.fam.build_model(self.cfg, seed)
+        self.box_dim, self.label_base = self.fam.box_dim, self.fam.label_base
         self.B, self.normalize = batch, normalize_intensity
-        self.z_offset = self.Z_OFFSET[family] if z_offset is None else z_offset
+        self.z_offset = self.fam.z_offset if z_offset is None else z_offset
         self.graph = graph and self.device.type == "cuda"
         if weights:
             self.model = load_weights(self.model, weights)
             calibrate_target = None
-        self.calibrate_target = self.FAMILIES[family] if calibrate_target == "auto" else calibrate_target
+        self.calibrate_target = self.fam.calibrate_target if calibrate_target == "auto" else calibrate_target
         self.max_points = max_points
         self.names = list(self.cfg.class_names)
         self._pipes: Dict[tuple, tuple] = {}
@@ -520,30 +502,18 @@ class LocalDetector3D(Detector3D):
         self._cpu = None
 
     # ----------------------------------------------------------------- GPU path
-    def _pipeline_cls(self):
-        if self.family == "second_iou":
-            from ..pipelines import SecondPipeline
-            return SecondPipeline
-        if self.family == "centerpoint":
-            from ..pipelines.centerpoint import CenterPointPipeline
-            return CenterPointPipeline
-        from ..pipelines import LidarPipeline
-        return LidarPipeline
-
     def _calibrated_pipeline(self, layout, max_points: int, sample: Optional[msgs.PointCloud2]):
         """A new pipeline for clouds of ``layout`` (<= max_points points); the
         first one built sets the random-init head prior from ``sample`` once."""
-        p = self._pipeline_cls()(self.model, batch=self.B, max_points=max_points, layout=layout,
-                                 z_offset=self.z_offset, normalize_intensity=self.normalize, device=self.device)
+        p = self.fam.pipeline_cls()(self.model, batch=self.B, max_points=max_points, layout=layout,
+                                    z_offset=self.z_offset, normalize_intensity=self.normalize, device=self.device)
         if self.calibrate_target is not None:
+            from ..pipelines.lidar import calibrate_on_cloud
+
             if sample is None:
                 sample = self._sample_cloud(0)
-            raw = torch.frombuffer(bytearray(sample.data), dtype=torch.uint8)
-            raw = raw[:min(raw.numel(), p.frame_bytes)]
-            for b in range(self.B):
-                p.data[b * p.frame_bytes: b * p.frame_bytes + raw.numel()].copy_(raw)
-            p.frame_n.fill_(min(sample.width * sample.height, p.max_points))
-            p.calibrate_detection_density(self.calibrate_target)
+            calibrate_on_cloud(p, torch.frombuffer(bytearray(sample.data), dtype=torch.uint8),
+                               sample.width * sample.height, self.calibrate_target)
             self.calibrate_target = None
         self.model = p.model
         return p
@@ -579,11 +549,8 @@ class LocalDetector3D(Detector3D):
 
     def _sample_cloud(self, seed: int):
         from ..ros.compat import create_cloud_xyzi
-        from ..utils.synthetic import LidarSpec, lidar_sweep
 
-        spec = (LidarSpec(rings=32, azimuth_steps=1800, sensor_height=1.8) if self.family == "centerpoint"
-                else LidarSpec(sensor_height=3.23))
-        pts = lidar_sweep(spec, seed)
+        pts = self.fam.sample_sweep(seed)
         return create_cloud_xyzi(np.frombuffer(pts.tobytes(), np.float32).reshape(-1, 4))
 
     @torch.no_grad()
@@ -601,7 +568,9 @@ class LocalDetector3D(Detector3D):
 
     def _frames_out(self, res) -> List[dict]:
         """Pipeline result → per-frame dicts in the sensor frame (z offset removed)."""
-        if self.family == "centerpoint":
+        from ..ops.centerpoint import CenterPointResult
+
+        if isinstance(res, CenterPointResult):  # per-task segments; per_image() already gives the served dicts
             per = res.per_image()
             for d in per:
                 d["pred_boxes"] = d["pred_boxes"].copy()
@@ -662,6 +631,7 @@ class LocalDetector3D(Detector3D):
         per-(frame, task) NMS segments (6 tasks x <= 83, ``nms_post_max``) are packed on
         the device into each frame's first ``count`` rows, in task order, with the 9-d
         det3d box order (the layout of ``CenterPointResult.per_image``)."""
+        from ..ops.centerpoint import CenterPointResult
         from ..ops.lidar import PointLayout
 
         if self.device.type != "cuda" or not data.is_cuda:
@@ -688,7 +658,7 @@ class LocalDetector3D(Detector3D):
                 slots[:k, :maxb].copy_(data[s:s + k])
                 p.frame_n[:k].copy_(npts[s:s + k].to(torch.int32))
                 res = run()
-                if self.family == "centerpoint":
+                if isinstance(res, CenterPointResult):
                     b, sc, lb, c = pack_task_segments(res, k, max_out)
                     box[s:s + k] = b
                     box[s:s + k, :, 2] -= self.z_offset
@@ -705,65 +675,44 @@ class LocalDetector3D(Detector3D):
 
     # ----------------------------------------------------------------- CPU path
     def _detect_cpu(self, cloud: msgs.PointCloud2) -> dict:
-        from ..models.common import fuse_model
-        from ..models.pointpillars import pillar_point_features, scatter_to_bev
-        from ..ops.lidar import AnchorPostprocess, voxelize_np
-        from ..ros.compat import cloud_to_numpy
-
-        if self.family != "pointpillars":
-            return self._detect_cpu_voxels(cloud)
-        if self._cpu is None:
-            self.model = fuse_model(self.model.eval()).float()
-            self._cpu = AnchorPostprocess(self.cfg, 1, device="cpu")
-        pts = cloud_to_numpy(cloud, normalize_intensity=self.normalize, z_offset=self.z_offset)
-        v, zyx, num, _ = voxelize_np(pts, self.cfg.voxel, 4)
-        if len(v) == 0:
-            return _empty3d()
-        coords = torch.from_numpy(np.pad(zyx, ((0, 0), (1, 0))).astype(np.int32))
-        feats = pillar_point_features(torch.from_numpy(v), torch.from_numpy(num.astype(np.int64)), coords,
-                                      self.cfg.voxel)
-        if self.calibrate_target is not None:
-            self._calibrate_cpu(feats, coords)
-        nx, ny, _ = self.cfg.voxel.grid_size
-        canvas = scatter_to_bev(self.model.vfe(feats), coords, 1, ny, nx, channels_last=False)
-        res = self._cpu.cpu(*self.model.bev_forward(canvas))
-        k = int(res.count[0])
-        box = np.asarray(res.box[0, :k], np.float32).copy()
-        box[:, 2] -= self.z_offset
-        return {"pred_boxes": box, "pred_scores": np.asarray(res.score[0, :k], np.float32),
-                "pred_labels": np.asarray(res.cls[0, :k]).astype(np.int64)}
-
-    def _detect_cpu_voxels(self, cloud: msgs.PointCloud2) -> dict:
-        """SECOND-IoU / CenterPoint on the CPU: the client-side voxeliser, then
-        the served model's CPU path (same code as the KServe ``second_iou`` /
-        ``centerpoint_pp`` models).  Random-init heads are not calibrated here."""
+        """Every family on the CPU: the client-side voxeliser, then the served model's CPU
+        path (same code as the KServe ``pointpillar_kitti`` / ``second_iou`` /
+        ``centerpoint_pp`` models) over this engine's module."""
         from ..models.common import fuse_model
         from ..ops.lidar import voxelize_np
         from ..ros.compat import cloud_to_numpy
 
         if self._cpu is None:
-            from ..server.models import CenterPointModel, SecondIoUModel
+            from ..server.models import VOXEL_MODELS
 
-            m = (SecondIoUModel if self.family == "second_iou" else CenterPointModel)(cfg=self.cfg, device="cpu")
+            m = VOXEL_MODELS[self.family](cfg=self.cfg, device="cpu")
             self.model = m.model = fuse_model(self.model.eval()).float()
             m.ready = True
             self._cpu = m
-            self.calibrate_target = None
         pts = cloud_to_numpy(cloud, normalize_intensity=self.normalize, z_offset=self.z_offset)
         v, zyx, num, _ = voxelize_np(pts, self.cfg.voxel, 4)
         if len(v) == 0:
             return _empty3d(self.box_dim)
         coords = np.pad(zyx, ((0, 0), (1, 0))).astype(np.int32)
+        if self.calibrate_target is not None:
+            self._calibrate_cpu(v, num, coords)
         out = self._cpu.execute({"voxels": v, "voxel_coords": coords, "voxel_num_points": num.astype(np.int32)}, None)
         out = dict(out)
         out["pred_boxes"] = np.asarray(out["pred_boxes"], np.float32).copy()
         out["pred_boxes"][:, 2] -= self.z_offset
         return out
 
-    def _calibrate_cpu(self, feats, coords):
-        """CPU twin of LidarPipeline.calibrate_detection_density (bias shift only)."""
-        from ..models.pointpillars import scatter_to_bev
+    def _calibrate_cpu(self, v, num, coords):
+        """CPU twin of LidarPipeline.calibrate_detection_density (bias shift only), written for
+        the PointPillars module; the other families' random-init heads are not calibrated here."""
+        from ..models.pointpillars import PointPillars, pillar_point_features, scatter_to_bev
 
+        if not isinstance(self.model, PointPillars):
+            self.calibrate_target = None
+            return
+        coords = torch.from_numpy(coords)
+        feats = pillar_point_features(torch.from_numpy(v), torch.from_numpy(num.astype(np.int64)), coords,
+                                      self.cfg.voxel)
         nx, ny, _ = self.cfg.voxel.grid_size
         cls, _, _ = self.model.bev_forward(scatter_to_bev(self.model.vfe(feats), coords, 1, ny, nx,
                                                           channels_last=False))

@@ -85,7 +85,7 @@ class EvaluateInference3D(BaseInference):
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset)
         self.class_names = class_names or list(getattr(self.engine, "names", []) or [])
-        self.label_base = 0 if getattr(self.engine, "family", "") == "centerpoint" else 1
+        self.label_base = getattr(self.engine, "label_base", 1)
         self.bus, self.conf_thres, self.gt_z_offset = bus, conf_thres, float(gt_z_offset)
         if gt_type not in ("jsk", "detection3d"):
             raise ValueError(f"gt_type {gt_type!r}: 'jsk' or 'detection3d'")

@@ -37,6 +37,17 @@ from ..ops.lidar import AnchorPostprocess, PillarEncoder, PointLayout, Voxelizer
 LAZY_CANVAS_CLEAR = os.environ.get("TCA_LAZY_CANVAS", "1") != "0"
 
 
+def calibrate_on_cloud(pipe, payload: torch.Tensor, npoints: int, target: float) -> None:
+    """Set a random-init head prior from one cloud: its payload bytes (uint8) go into every
+    frame slot of ``pipe`` (any of the LiDAR families' pipelines), then
+    ``calibrate_detection_density(target)`` runs on them."""
+    raw = payload[:min(payload.numel(), pipe.frame_bytes)]
+    for b in range(pipe.B):
+        pipe.data[b * pipe.frame_bytes: b * pipe.frame_bytes + raw.numel()].copy_(raw)
+    pipe.frame_n.fill_(min(npoints, pipe.max_points))
+    pipe.calibrate_detection_density(target)
+
+
 class LidarPipeline:
     def __init__(self, model: Optional[PointPillars] = None, batch: int = 16, max_points: int = 131072,
                  layout: Optional[PointLayout] = None, z_offset: float = 1.5, normalize_intensity: bool = True,

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ..config.lidar import PointPillarsConfig, VoxelConfig
+from ..config.lidar import LIDAR_FAMILIES, PointPillarsConfig
 from ..proto import model_config_pb2 as mc
 from .model import PROFILE, InferError, ServedModel, tensor_spec
 from ..utils.model_store import load_state_dict
@@ -324,11 +324,12 @@ class _YoloPlan:
         return finish
 
 
-def check_voxel_shapes(inputs, P: int, max_voxels: int) -> int:
-    """The shape part of :func:`check_voxel_inputs` (no value reads) → V."""
+def check_voxel_shapes(inputs, P: int, max_voxels: int, features: int = 4) -> int:
+    """The shape part of :func:`check_voxel_inputs` (no value reads) → V.  ``features``: the
+    width the model declares, for the message; 4 columns (x, y, z, intensity) and up are taken."""
     vox, co, n = inputs["voxels"], inputs["voxel_coords"], inputs["voxel_num_points"]
     if vox.ndim != 3 or vox.shape[1] != P or vox.shape[2] < 4:
-        raise InferError(f"voxels must be [-1, {P}, 4], got {list(vox.shape)}")
+        raise InferError(f"voxels must be [-1, {P}, {features}], got {list(vox.shape)}")
     V = vox.shape[0]
     if V > max_voxels:
         raise InferError(f"{V} voxels > max_voxels {max_voxels}")
@@ -339,7 +340,7 @@ def check_voxel_shapes(inputs, P: int, max_voxels: int) -> int:
     return V
 
 
-def check_voxel_inputs(inputs: Dict[str, np.ndarray], P: int, max_voxels: int, grid_size) -> int:
+def check_voxel_inputs(inputs: Dict[str, np.ndarray], P: int, max_voxels: int, grid_size, features: int = 4) -> int:
     """Validate one request's (voxels, voxel_coords, voxel_num_points) against the
     model's voxel grid before any byte reaches the device.  The GPU consumers index
     ``(b * ny + y) * nx + x`` (pillar scatter, canvas clear, sparse-conv rulebook)
@@ -347,20 +348,11 @@ def check_voxel_inputs(inputs: Dict[str, np.ndarray], P: int, max_voxels: int, g
     another request's canvas slot of a dynamic batch, or outside the allocation.
     Returns V.  Reference contract: ``examples/pointpillar_kitti/config.pbtxt:27-52``
     (voxels [-1, P, 4], voxel_coords [-1, 4] = (b, z, y, x), voxel_num_points [-1])."""
-    vox, co, n = inputs["voxels"], inputs["voxel_coords"], inputs["voxel_num_points"]
-    dev = isinstance(co, torch.Tensor)
-    if vox.ndim != 3 or vox.shape[1] != P or vox.shape[2] < 4:
-        raise InferError(f"voxels must be [-1, {P}, 4], got {list(vox.shape)}")
-    V = vox.shape[0]
-    if V > max_voxels:
-        raise InferError(f"{V} voxels > max_voxels {max_voxels}")
-    if co.ndim != 2 or co.shape[0] != V or co.shape[1] != 4:
-        raise InferError(f"voxel_coords must be [{V}, 4], got {list(co.shape)}")
-    if n.ndim != 1 or n.shape[0] != V:
-        raise InferError(f"voxel_num_points must be [{V}], got {list(n.shape)}")
+    V = check_voxel_shapes(inputs, P, max_voxels, features)
+    co, n = inputs["voxel_coords"], inputs["voxel_num_points"]
     if V:
         nx, ny, nz = (int(g) for g in grid_size)
-        if dev:  # device shared memory: the reductions on the GPU, one small copy back
+        if isinstance(co, torch.Tensor):  # device shared memory: the reductions on the GPU, one small copy back
             lo, hi = torch.aminmax(co.to(torch.int64), dim=0)
             nlo, nhi = torch.aminmax(n.to(torch.int64))
             v = torch.cat([lo, hi, nlo.view(1), nhi.view(1)]).cpu().tolist()
@@ -593,25 +585,29 @@ class YoloV5Model(ServedModel):
         return _pick(self.plan_sets[inst], len(batch)).issue([x["images"] for x in batch], dsts)
 
 
-class PointPillarsModel(ServedModel):
-    def __init__(self, name: str = "pointpillar_kitti", cfg: Optional[PointPillarsConfig] = None, device="auto",
-                 weights: Optional[str] = None, seed: int = 0, calibrate_target: float = 2000.0,
-                 batch: int = 16, instances: Optional[int] = None, pipeline_depth: Optional[int] = None):
+class _VoxelModel(ServedModel):
+    """What the three served LiDAR models share, from their family's record
+    (``config.lidar.LIDAR_FAMILIES``): the tensor contract (inputs ``voxels`` FP32
+    [-1, P, features], ``voxel_coords`` INT32 [-1, 4] (b, z, y, x), ``voxel_num_points``
+    INT32 [-1]; outputs ``pred_boxes`` FP32 [-1, box_dim], ``pred_scores`` FP32 [-1],
+    ``pred_labels`` INT64 [-1]), the voxel geometry published in ``ModelConfig.parameters``
+    so clients voxelise with the model's own parameters, the request check, and the load."""
+
+    def __init__(self, family: str, name: str, cfg, device, weights: Optional[str], seed: int,
+                 calibrate_target: float):
         super().__init__(name)
-        self.batch = batch  # dynamic batching: concurrent requests share one batch-`batch` pass
-        self.instances = _instances(instances)
-        self.pipeline_depth = _depth(pipeline_depth)
-        self.cfg = cfg or PointPillarsConfig()
+        self.fam = LIDAR_FAMILIES[family]
+        self.cfg = cfg or self.fam.config()
         self.device = _device(device)
         self.weights, self.seed, self.calibrate_target = weights, seed, calibrate_target
         self.P = self.cfg.voxel.max_points_per_voxel
 
     def inputs(self):
-        return [tensor_spec("voxels", "FP32", [-1, self.P, 4]), tensor_spec("voxel_coords", "INT32", [-1, 4]),
-                tensor_spec("voxel_num_points", "INT32", [-1])]
+        return [tensor_spec("voxels", "FP32", [-1, self.P, self.fam.point_features]),
+                tensor_spec("voxel_coords", "INT32", [-1, 4]), tensor_spec("voxel_num_points", "INT32", [-1])]
 
     def outputs(self):
-        return [tensor_spec("pred_boxes", "FP32", [-1, 7], output=True),
+        return [tensor_spec("pred_boxes", "FP32", [-1, self.fam.box_dim], output=True),
                 tensor_spec("pred_scores", "FP32", [-1], output=True),
                 tensor_spec("pred_labels", "INT64", [-1], output=True)]
 
@@ -621,43 +617,75 @@ class PointPillarsModel(ServedModel):
     def config(self):
         c = super().config()
         v = self.cfg.voxel
-        for k, val in (("point_cloud_range", list(v.point_cloud_range)), ("voxel_size", list(v.voxel_size)),
-                       ("max_points_per_voxel", v.max_points_per_voxel), ("max_voxels", v.max_voxels),
-                       ("class_names", list(self.cfg.class_names))):
+        params = {"point_cloud_range": list(v.point_cloud_range), "voxel_size": list(v.voxel_size),
+                  "max_points_per_voxel": v.max_points_per_voxel, "max_voxels": v.max_voxels,
+                  "class_names": list(self.cfg.class_names)}
+        if self.fam.point_features != 4:  # clients voxelise x, y, z, intensity unless told otherwise
+            params["num_point_features"] = self.fam.point_features
+        for k, val in params.items():
             c.parameters[k].string_value = json.dumps(val)
         return c
 
+    def _check(self, inputs) -> int:
+        """Shapes, cell coordinates and point counts of one request, before any byte of it is
+        copied to the device → V."""
+        v = self.cfg.voxel
+        return check_voxel_inputs(inputs, self.P, v.max_voxels, v.grid_size, self.fam.point_features)
+
+    @staticmethod
+    def _response(res) -> Dict[str, np.ndarray]:
+        """Frame 0 of an ``NmsResult`` as the served outputs."""
+        k = int(res.count[0])
+        return {"pred_boxes": res.box[0, :k].cpu().numpy().astype(np.float32),
+                "pred_scores": res.score[0, :k].cpu().numpy().astype(np.float32),
+                "pred_labels": res.cls[0, :k].cpu().numpy().astype(np.int64)}
+
+    def _pipeline_kwargs(self) -> dict:
+        """Further keyword arguments of the family's pipeline class."""
+        return {}
+
     def load(self):
-        from ..models.pointpillars import build_pointpillars
-        model = build_pointpillars(self.cfg, self.seed)
+        fam = self.fam
+        model = fam.build_model(self.cfg, self.seed)
         if self.weights:
             model.load_state_dict(load_state_dict(self.weights, getattr(self, "weights_sha256", None)))
         if self.device.type == "cuda":
-            from ..pipelines.lidar import LidarPipeline
-            from ..utils.synthetic import LidarSpec, lidar_sweep
+            from ..pipelines.lidar import calibrate_on_cloud
 
-            spec = LidarSpec(sensor_height=3.23)
-            maxp = ((spec.points_per_sweep + 1023) // 1024) * 1024
-            self.pipe = LidarPipeline(model, batch=1, max_points=maxp, device=self.device)
-            if not self.weights:
-                c = lidar_sweep(spec, self.seed)
-                raw = torch.from_numpy(c.view(np.uint8).reshape(-1))
-                self.pipe.data[: raw.numel()].copy_(raw)
-                self.pipe.frame_n.fill_(c.shape[0])
-                self.pipe.calibrate_detection_density(self.calibrate_target)
+            maxp = ((fam.sweep[0] * fam.sweep[1] + 1023) // 1024) * 1024
+            self.pipe = fam.pipeline_cls()(model, batch=1, max_points=maxp, device=self.device,
+                                           z_offset=fam.z_offset, **self._pipeline_kwargs())
+            if not self.weights:  # random init: set the head prior on the family's synthetic sweep
+                c = fam.sample_sweep(self.seed)
+                calibrate_on_cloud(self.pipe, torch.from_numpy(c.view(np.uint8).reshape(-1)), c.shape[0],
+                                   self.calibrate_target)
             self.model = self.pipe.model
-            sizes = sorted({b for b in PLAN_SIZES if b <= max(1, self.batch)} | {max(1, self.batch)})
-            self.plan_sets = [{b: _PointPillarsPlan(self.model, self.cfg, b, self.device) for b in sizes}
-                              for _ in range(self.plan_set_count())]
-            self.plans = self.plan_sets[0]
-            self.dynamic_batch = max(sizes)
+            self._load_gpu()
         else:
             from ..models.common import fuse_model
             self.model = fuse_model(model.eval())
         self.ready = True
 
-    def _check(self, inputs):
-        return check_voxel_inputs(inputs, self.P, self.cfg.voxel.max_voxels, self.cfg.voxel.grid_size)
+    def _load_gpu(self) -> None:
+        """The subclass's own device buffers / captured plans over ``self.pipe`` and ``self.model``."""
+
+
+class PointPillarsModel(_VoxelModel):
+    def __init__(self, name: str = "pointpillar_kitti", cfg: Optional[PointPillarsConfig] = None, device="auto",
+                 weights: Optional[str] = None, seed: int = 0,
+                 calibrate_target: float = LIDAR_FAMILIES["pointpillars"].calibrate_target, batch: int = 16,
+                 instances: Optional[int] = None, pipeline_depth: Optional[int] = None):
+        super().__init__("pointpillars", name, cfg, device, weights, seed, calibrate_target)
+        self.batch = batch  # dynamic batching: concurrent requests share one batch-`batch` pass
+        self.instances = _instances(instances)
+        self.pipeline_depth = _depth(pipeline_depth)
+
+    def _load_gpu(self):
+        sizes = sorted({b for b in PLAN_SIZES if b <= max(1, self.batch)} | {max(1, self.batch)})
+        self.plan_sets = [{b: _PointPillarsPlan(self.model, self.cfg, b, self.device) for b in sizes}
+                          for _ in range(self.plan_set_count())]
+        self.plans = self.plan_sets[0]
+        self.dynamic_batch = max(sizes)
 
     device_inputs = True
 
@@ -697,25 +725,20 @@ class PointPillarsModel(ServedModel):
             if isinstance(r, BaseException):
                 raise r
             return r
-        else:
-            from ..models.pointpillars import pillar_point_features, scatter_to_bev
-            from ..ops.lidar import AnchorPostprocess
-            v = torch.from_numpy(np.require(vox[..., :4], np.float32, ['C', 'W']))
-            c = torch.from_numpy(np.require(co, np.int32, ['C', 'W'])).clone()
-            c[:, 0] = 0
-            f = pillar_point_features(v, torch.from_numpy(n.astype(np.int64)), c, self.cfg.voxel)
-            pf = self.model.vfe(f)
-            nx, ny, _ = self.cfg.voxel.grid_size
-            canvas = scatter_to_bev(pf, c, 1, ny, nx, channels_last=False)
-            cls, box, dr = self.model.bev_forward(canvas)
-            res = AnchorPostprocess(self.cfg, 1, device="cpu").cpu(cls, box, dr)
-        k = int(res.count[0])
-        return {"pred_boxes": res.box[0, :k].cpu().numpy().astype(np.float32),
-                "pred_scores": res.score[0, :k].cpu().numpy().astype(np.float32),
-                "pred_labels": res.cls[0, :k].cpu().numpy().astype(np.int64)}
+        from ..models.pointpillars import pillar_point_features, scatter_to_bev
+        from ..ops.lidar import AnchorPostprocess
+        v = torch.from_numpy(np.require(vox[..., :4], np.float32, ['C', 'W']))
+        c = torch.from_numpy(np.require(co, np.int32, ['C', 'W'])).clone()
+        c[:, 0] = 0
+        f = pillar_point_features(v, torch.from_numpy(n.astype(np.int64)), c, self.cfg.voxel)
+        pf = self.model.vfe(f)
+        nx, ny, _ = self.cfg.voxel.grid_size
+        canvas = scatter_to_bev(pf, c, 1, ny, nx, channels_last=False)
+        cls, box, dr = self.model.bev_forward(canvas)
+        return self._response(AnchorPostprocess(self.cfg, 1, device="cpu").cpu(cls, box, dr))
 
 
-class SecondIoUModel(ServedModel):
+class SecondIoUModel(_VoxelModel):
     """``second_iou`` — OpenPCDet SECONDNetIoU (``examples/second_iou/config.pbtxt``,
     KIND_GPU; ``examples/second_iou/1/model.py``): inputs ``voxels`` FP32
     [-1, 5, 4], ``voxel_coords`` INT32 [-1, 4] (b, z, y, x), ``voxel_num_points``
@@ -726,70 +749,20 @@ class SecondIoUModel(ServedModel):
     proposal top-k + rotated NMS, RoI grid pool + FC IoU head, final NMS."""
 
     def __init__(self, name: str = "second_iou", cfg=None, device="auto", weights: Optional[str] = None,
-                 seed: int = 0, calibrate_target: float = 60.0):
-        from ..config.lidar import SecondIoUConfig
+                 seed: int = 0, calibrate_target: float = LIDAR_FAMILIES["second_iou"].calibrate_target):
+        super().__init__("second_iou", name, cfg, device, weights, seed, calibrate_target)
 
-        super().__init__(name)
-        self.cfg = cfg or SecondIoUConfig()
-        self.device = _device(device)
-        self.weights, self.seed, self.calibrate_target = weights, seed, calibrate_target
-        self.P = self.cfg.voxel.max_points_per_voxel
-
-    def inputs(self):
-        return [tensor_spec("voxels", "FP32", [-1, self.P, 4]), tensor_spec("voxel_coords", "INT32", [-1, 4]),
-                tensor_spec("voxel_num_points", "INT32", [-1])]
-
-    def outputs(self):
-        return [tensor_spec("pred_boxes", "FP32", [-1, 7], output=True),
-                tensor_spec("pred_scores", "FP32", [-1], output=True),
-                tensor_spec("pred_labels", "INT64", [-1], output=True)]
-
-    def instance_kind(self):
-        return mc.ModelInstanceGroup.KIND_GPU if self.device.type == "cuda" else mc.ModelInstanceGroup.KIND_CPU
-
-    def config(self):
-        c = super().config()
-        v = self.cfg.voxel
-        for k, val in (("point_cloud_range", list(v.point_cloud_range)), ("voxel_size", list(v.voxel_size)),
-                       ("max_points_per_voxel", v.max_points_per_voxel), ("max_voxels", v.max_voxels),
-                       ("class_names", list(self.cfg.class_names))):
-            c.parameters[k].string_value = json.dumps(val)
-        return c
-
-    def load(self):
-        from ..models.common import fuse_model
-        from ..models.second import build_second_iou
-
-        model = build_second_iou(self.cfg, self.seed)
-        if self.weights:
-            model.load_state_dict(load_state_dict(self.weights, getattr(self, "weights_sha256", None)))
-        if self.device.type == "cuda":
-            from ..pipelines.second import SecondPipeline
-            from ..utils.synthetic import LidarSpec, lidar_sweep
-
-            spec = LidarSpec(sensor_height=3.23)
-            maxp = ((spec.points_per_sweep + 1023) // 1024) * 1024
-            self.pipe = SecondPipeline(model, batch=1, max_points=maxp, device=self.device, z_offset=1.5)
-            if not self.weights:
-                c = lidar_sweep(spec, self.seed)
-                raw = torch.from_numpy(c.view(np.uint8).reshape(-1))
-                self.pipe.data[: raw.numel()].copy_(raw)
-                self.pipe.frame_n.fill_(c.shape[0])
-                self.pipe.calibrate_detection_density(self.calibrate_target)
-            V = self.cfg.voxel.max_voxels
-            self.voxels = torch.zeros((V, self.P, 4), dtype=torch.float32, device=self.device)
-            self.coords = torch.zeros((V, 4), dtype=torch.int32, device=self.device)
-            self.nump = torch.zeros((V,), dtype=torch.int32, device=self.device)
-            self.vcount = torch.zeros((1,), dtype=torch.int32, device=self.device)
-            self.model = self.pipe.model
-        else:
-            self.model = fuse_model(model.eval())
-        self.ready = True
+    def _load_gpu(self):
+        V = self.cfg.voxel.max_voxels
+        self.voxels = torch.zeros((V, self.P, 4), dtype=torch.float32, device=self.device)
+        self.coords = torch.zeros((V, 4), dtype=torch.int32, device=self.device)
+        self.nump = torch.zeros((V,), dtype=torch.int32, device=self.device)
+        self.vcount = torch.zeros((1,), dtype=torch.int32, device=self.device)
 
     @torch.no_grad()
     def execute(self, inputs, requested):
         vox, co, n = inputs["voxels"], inputs["voxel_coords"], inputs["voxel_num_points"]
-        V = check_voxel_inputs(inputs, self.P, self.cfg.voxel.max_voxels, self.cfg.voxel.grid_size)
+        V = self._check(inputs)
         v = torch.from_numpy(np.require(vox[..., :4], np.float32, ['C', 'W']))
         c = torch.from_numpy(np.require(co, np.int32, ['C', 'W'])).clone()
         c[:, 0] = 0
@@ -799,11 +772,7 @@ class SecondIoUModel(ServedModel):
             self.coords[:V].copy_(c)
             self.nump[:V].copy_(nn_)
             self.vcount.fill_(V)
-            res = self.pipe.run_voxels(self.voxels, self.nump, self.coords, self.vcount)
-            k = int(res.count[0])
-            return {"pred_boxes": res.box[0, :k].cpu().numpy().astype(np.float32),
-                    "pred_scores": res.score[0, :k].cpu().numpy().astype(np.float32),
-                    "pred_labels": res.cls[0, :k].cpu().numpy().astype(np.int64)}
+            return self._response(self.pipe.run_voxels(self.voxels, self.nump, self.coords, self.vcount))
         from ..models.second import postprocess_reference, proposal_config
         from ..ops.lidar import AnchorPostprocess
         m = self.model
@@ -816,7 +785,7 @@ class SecondIoUModel(ServedModel):
                 "pred_labels": lb.astype(np.int64)}
 
 
-class CenterPointModel(ServedModel):
+class CenterPointModel(_VoxelModel):
     """``centerpoint_pp`` — det3d CenterPoint-PointPillars (nuScenes, 10 classes):
     inputs ``voxels`` FP32 [-1, 20, 5] (x, y, z, r, time lag), ``voxel_coords``
     INT32 [-1, 4] (b, z, y, x), ``voxel_num_points`` INT32 [-1]; outputs
@@ -827,78 +796,27 @@ class CenterPointModel(ServedModel):
     voxels, fused RPN + CenterHead, K12 decode + per-task rotated NMS."""
 
     def __init__(self, name: str = "centerpoint_pp", cfg=None, device="auto", weights: Optional[str] = None,
-                 seed: int = 0, calibrate_target: float = 1000.0, class_thresh=None):
-        from ..config.lidar import CenterPointConfig
-
-        super().__init__(name)
-        self.cfg = cfg or CenterPointConfig()
-        self.device = _device(device)
-        self.weights, self.seed, self.calibrate_target = weights, seed, calibrate_target
+                 seed: int = 0, calibrate_target: float = LIDAR_FAMILIES["centerpoint"].calibrate_target,
+                 class_thresh=None):
+        super().__init__("centerpoint", name, cfg, device, weights, seed, calibrate_target)
         self.class_thresh = class_thresh
-        self.P = self.cfg.voxel.max_points_per_voxel
 
-    def inputs(self):
-        return [tensor_spec("voxels", "FP32", [-1, self.P, 5]), tensor_spec("voxel_coords", "INT32", [-1, 4]),
-                tensor_spec("voxel_num_points", "INT32", [-1])]
+    def _pipeline_kwargs(self):
+        return {"class_thresh": self.class_thresh}
 
-    def outputs(self):
-        return [tensor_spec("pred_boxes", "FP32", [-1, 9], output=True),
-                tensor_spec("pred_scores", "FP32", [-1], output=True),
-                tensor_spec("pred_labels", "INT64", [-1], output=True)]
-
-    def instance_kind(self):
-        return mc.ModelInstanceGroup.KIND_GPU if self.device.type == "cuda" else mc.ModelInstanceGroup.KIND_CPU
-
-    def config(self):
-        c = super().config()
-        v = self.cfg.voxel
-        for k, val in (("point_cloud_range", list(v.point_cloud_range)), ("voxel_size", list(v.voxel_size)),
-                       ("max_points_per_voxel", v.max_points_per_voxel), ("max_voxels", v.max_voxels),
-                       ("num_point_features", 5), ("class_names", list(self.cfg.class_names))):
-            c.parameters[k].string_value = json.dumps(val)
-        return c
-
-    def load(self):
-        from ..models.centerpoint import build_centerpoint
-        from ..models.common import fuse_model
-
-        model = build_centerpoint(self.cfg, self.seed)
-        if self.weights:
-            model.load_state_dict(load_state_dict(self.weights, getattr(self, "weights_sha256", None)))
-        if self.device.type == "cuda":
-            from ..pipelines.centerpoint import CenterPointPipeline
-            from ..utils.synthetic import LidarSpec, lidar_sweep
-
-            spec = LidarSpec(rings=32, azimuth_steps=1800, sensor_height=1.8)
-            maxp = ((spec.points_per_sweep + 1023) // 1024) * 1024
-            self.pipe = CenterPointPipeline(model, batch=1, max_points=maxp, device=self.device,
-                                            class_thresh=self.class_thresh)
-            if not self.weights:
-                c = lidar_sweep(spec, self.seed)
-                raw = torch.from_numpy(c.view(np.uint8).reshape(-1))
-                self.pipe.data[: raw.numel()].copy_(raw)
-                self.pipe.frame_n.fill_(c.shape[0])
-                self.pipe.calibrate_detection_density(self.calibrate_target)
-            V = self.cfg.voxel.max_voxels
-            self.voxels = torch.zeros((1, V, self.P, 5), dtype=torch.float32, device=self.device)
-            self.coords = torch.zeros((1, V, 4), dtype=torch.int32, device=self.device)
-            self.nump = torch.zeros((1, V), dtype=torch.int32, device=self.device)
-            self.vcount = torch.zeros((1,), dtype=torch.int32, device=self.device)
-            self.pipe.enc.clear(self.pipe.vox)
-            self.model = self.pipe.model
-        else:
-            self.model = fuse_model(model.eval())
-        self.ready = True
+    def _load_gpu(self):
+        V = self.cfg.voxel.max_voxels
+        self.voxels = torch.zeros((1, V, self.P, self.fam.point_features), dtype=torch.float32, device=self.device)
+        self.coords = torch.zeros((1, V, 4), dtype=torch.int32, device=self.device)
+        self.nump = torch.zeros((1, V), dtype=torch.int32, device=self.device)
+        self.vcount = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.pipe.enc.clear(self.pipe.vox)
 
     @torch.no_grad()
     def execute(self, inputs, requested):
         vox, co, n = inputs["voxels"], inputs["voxel_coords"], inputs["voxel_num_points"]
-        V = vox.shape[0]
-        if vox.shape[1] != self.P or vox.shape[2] < 4:
-            raise InferError(f"voxels must be [-1, {self.P}, 5], got {list(vox.shape)}")
-        if V > self.cfg.voxel.max_voxels:
-            raise InferError(f"{V} voxels > max_voxels {self.cfg.voxel.max_voxels}")
-        F_ = min(vox.shape[2], 5)
+        V = self._check(inputs)  # the PFN scatter and the canvas clear index the canvas with these cells
+        F_ = min(vox.shape[2], self.fam.point_features)
         if self.device.type == "cuda":
             from ..ops.conv import NHWC
 
@@ -918,7 +836,7 @@ class CenterPointModel(ServedModel):
             from ..models.pointpillars import scatter_to_bev
             from ..ops.centerpoint import CenterPointPostprocess
 
-            v = torch.zeros((V, self.P, 5))
+            v = torch.zeros((V, self.P, self.fam.point_features))
             v[..., :F_] = torch.from_numpy(np.require(vox[..., :F_], np.float32, ['C', 'W']))
             c = torch.from_numpy(np.require(co, np.int32, ['C', 'W'])).clone()
             c[:, 0] = 0
@@ -930,6 +848,10 @@ class CenterPointModel(ServedModel):
             pp = CenterPointPostprocess(self.cfg, 1, [16 * t for t in range(len(mo))], "cpu", self.class_thresh)
             out = pp(head.permute(0, 2, 3, 1)).per_image()[0]
         return out
+
+
+# family (a key of config.lidar.LIDAR_FAMILIES) -> its served model
+VOXEL_MODELS = {"pointpillars": PointPillarsModel, "second_iou": SecondIoUModel, "centerpoint": CenterPointModel}
 
 
 class _DetectronPlan:

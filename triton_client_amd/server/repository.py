@@ -14,6 +14,7 @@ import threading
 from pathlib import Path
 from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
+from ..config.lidar import LIDAR_FAMILIES, lidar_family
 from .model import EchoModel, ServedModel
 
 Factory = Callable[..., ServedModel]
@@ -26,44 +27,23 @@ def _yolo(name, variant="n", nc=80, img=640):
     return f
 
 
-def _pointpillars(name):
+def _lidar(name):
     def f(device="auto", **kw):
-        from .models import PointPillarsModel
-        return PointPillarsModel(name, device=device, **kw)
+        from .models import VOXEL_MODELS
+        return VOXEL_MODELS[lidar_family(name)](name, device=device, **kw)
     return f
 
 
 def _family(name: str) -> Optional[str]:
+    """Camera families by their name rules, then a LiDAR family (a key of LIDAR_FAMILIES)."""
     n = name.lower()
     if "yolov4" in n:
         return "yolov4"
     if "yolo" in n or "weed" in n:
         return "yolo"
-    if "pointpillar" in n or "pillar" in n:
-        return "pointpillars"
     if "retina" in n or "fcos" in n or "detectron" in n or n == "test_model":
         return "detectron"
-    if "centerpoint" in n:
-        return "centerpoint"
-    if "second" in n:
-        return "second_iou"
-    if "echo" in n:
-        return "echo"
-    return None
-
-
-def _second(name):
-    def f(device="auto", **kw):
-        from .models import SecondIoUModel
-        return SecondIoUModel(name, device=device, **kw)
-    return f
-
-
-def _centerpoint(name):
-    def f(device="auto", **kw):
-        from .models import CenterPointModel
-        return CenterPointModel(name, device=device, **kw)
-    return f
+    return lidar_family(name, default=None) or ("echo" if "echo" in n else None)
 
 
 def _detectron(name, arch, nc=80):
@@ -85,16 +65,16 @@ FACTORIES: Dict[str, Factory] = {
     "YOLOv5n": _yolo("YOLOv5n", "n", 80, 640),
     "YOLOv5nCROP": _yolo("YOLOv5nCROP", "n", 2, 512),
     "weed_detector": _yolo("weed_detector", "n", 2, 512),
-    "pointpillar_kitti": _pointpillars("pointpillar_kitti"),
-    "pointpillar_python": _pointpillars("pointpillar_python"),
-    "centerpoint_pp": _centerpoint("centerpoint_pp"),
-    "second_iou": _second("second_iou"),  # examples/second_iou/config.pbtxt
+    "pointpillar_kitti": _lidar("pointpillar_kitti"),
+    "pointpillar_python": _lidar("pointpillar_python"),
+    "centerpoint_pp": _lidar("centerpoint_pp"),
+    "second_iou": _lidar("second_iou"),  # examples/second_iou/config.pbtxt
     "YOLOv4": _yolov4("YOLOv4"),  # examples/YOLOv4/config.pbtxt
     "test_model": _detectron("test_model", "retinanet"),  # examples/RetinaNet_detectron/config.pbtxt
     "RetinaNet_detectron": _detectron("RetinaNet_detectron", "retinanet"),
     "FCOS_detectron": _detectron("FCOS_detectron", "fcos"),
     "fcos_weed_detector": _detectron("fcos_weed_detector", "fcos", 2),  # main.py:75 (weeds, maize)
-    "centerpoint": _centerpoint("centerpoint"),
+    "centerpoint": _lidar("centerpoint"),
     "echo": lambda device="auto", **kw: EchoModel("echo"),
 }
 
@@ -211,15 +191,8 @@ class ModelRepository:
                 dims = list(cfg.input[0].dims)
                 m = DetectronModel(name, "fcos" if "fcos" in name.lower() else "retinanet", tuple(dims[-2:]),
                                    device=device)
-            elif fam == "pointpillars":
-                from .models import PointPillarsModel
-                m = PointPillarsModel(name, device=device)
-            elif fam == "centerpoint":
-                from .models import CenterPointModel
-                m = CenterPointModel(name, device=device)
-            elif fam == "second_iou":
-                from .models import SecondIoUModel
-                m = SecondIoUModel(name, device=device)
+            elif fam in LIDAR_FAMILIES:
+                m = _lidar(name)(device=device)
             else:
                 continue
             weights, sha = _weights_for(os.path.join(path, entry), cfg)
