@@ -100,6 +100,9 @@ def main():
     ap.add_argument("--camera-tracks", action="store_true",
                     help="camera side: also track the detections and publish them with their track ids "
                          "(RosInference tracks_topic; the frames are stamped 1/30 s apart)")
+    ap.add_argument("--rectify", action="store_true",
+                    help="camera side: rectify every frame under a synthetic barrel-distortion camera model of the "
+                         "frame's size (RosInference rectify=; on the GPU unless TCA_DEVICE_RECTIFY=0)")
     ap.add_argument("--lidar", type=int, default=512, help="PointCloud2 messages (0: skip)")
     ap.add_argument("--bev", action="store_true",
                     help="LiDAR side: also publish the bird's-eye-view Image of every cloud (RosInference3D bev_topic)")
@@ -191,6 +194,7 @@ def main():
             opts = JpegOptions(quality=a.jpeg_quality, subsampling=a.jpeg_subsampling)
         drv = RosInference(engine=eng2, params={"sub_topic": "/cam", "pub_topic": "/cam_out"}, bus=bus,
                            batch=a.batch, workers=a.workers, metrics=st, queue_size=window, compressed=opts,
+                           **({"rectify": _barrel_model(H, W)} if a.rectify else {}),
                            **({"tracks_topic": "/cam_tracks"} if a.camera_tracks else {}))
         drv.start_inference(spin=False)
         out_type = msgs.CompressedImage if opts is not None else msgs.Image
@@ -206,6 +210,9 @@ def main():
                          "output": (f"annotated CompressedImage JPEG q{a.jpeg_quality} {a.jpeg_subsampling}"
                                     if opts is not None else "annotated Image") + " + Detection2DArray",
                          "published_bytes_per_frame": round(sum(sizes) / max(1, len(sizes))), "stages": st.summary()}
+        if a.rectify:
+            out["camera"]["output"] += f", rectified ({drv.rectifier().kind})"
+            out["camera"]["rectifier"] = drv.rectifier().kind
         if a.camera_tracks:
             trk = drv.tracker()
             ts = trk.state()
@@ -328,6 +335,16 @@ def _camera_messages(H, W, n, encoding=None):
         jpegs.append(buf.getvalue())
     return [msgs.CompressedImage(header=header(i), format="jpeg", data=jpegs[i % 8])
             for i in range(n)]
+
+
+def _barrel_model(H, W):
+    """A wide-angle lens of the frame's size: focal length 0.6 W, barrel distortion that moves the
+    corners over a hundred pixels at 1280 x 720, a little tangential distortion."""
+    from triton_client_amd.ops.rectify import CameraModel
+
+    f = 0.6 * W
+    K = [[f, 0.0, (W - 1) / 2.0], [0.0, f, (H - 1) / 2.0], [0.0, 0.0, 1.0]]
+    return CameraModel(width=W, height=H, K=K, D=[-0.28, 0.07, 0.0005, -0.0003, 0.0], model="plumb_bob")
 
 
 def _kitti_like_calibration():

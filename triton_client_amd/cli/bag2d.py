@@ -6,7 +6,7 @@ import os
 import sys
 
 from .common import (DATA, add_framework_flags, add_reference_flags, add_track2d_flags, jpeg_options, load_params,
-                     setup_logging, track2d_options)
+                     rectify_model, setup_logging, track2d_options)
 from .engines import engine_2d, export_if_asked, maybe_data_parallel
 
 
@@ -37,6 +37,9 @@ def main(argv=None) -> int:
         if info is not None and flags.publish_compressed:  # every rank stops here, before any serves
             raise SystemExit("--publish-compressed is not available with data-parallel ranks (raw frames travel "
                              "between them); run one process per GPU")
+        if info is not None and flags.rectify:
+            raise SystemExit("--rectify is not available with data-parallel ranks (the sensor's frames travel "
+                             "between them); run one process per GPU")
         if info is not None and not info.is_main:  # worker rank: serve shards until rank 0 is done
             engine.serve()
             from ..parallel.dp import shutdown
@@ -45,7 +48,8 @@ def main(argv=None) -> int:
     drv = BagInference2D(channel, client, engine=engine, params=params, bagfile=flags.bag, out_dir=flags.out or None,
                          out_bag=flags.out_bag, batch=max(1, flags.frames_per_step), save_png=bool(flags.out),
                          start_seq=flags.start_seq, max_frames=flags.max_frames, compressed=jpeg_options(flags),
-                         tracks_topic=flags.tracks_topic or None, track_options=track2d_options(flags))
+                         tracks_topic=flags.tracks_topic or None, track_options=track2d_options(flags),
+                         rectify=rectify_model(flags))
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

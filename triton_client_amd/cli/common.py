@@ -87,6 +87,10 @@ def add_framework_flags(p: argparse.ArgumentParser, params_default: str, three_d
         g.add_argument("--jpeg-quality", type=int, default=90, help="--publish-compressed: JPEG quality 1..100")
         g.add_argument("--jpeg-subsampling", choices=["4:2:0", "4:2:2", "4:4:4"], default="4:2:0",
                        help="--publish-compressed: chroma subsampling")
+        g.add_argument("--rectify", default="", metavar="CAMERA.yaml",
+                       help="rectify every frame from this camera_calibration YAML before detection: the annotated "
+                            "frame, the detections and the tracks are in rectified pixels (local GPU engine: on the "
+                            "device; not with data-parallel ranks)")
 
 
 def load_params(path: Optional[str], server: Optional[str] = None) -> dict:
@@ -152,6 +156,16 @@ def jpeg_options(flags):
     from ..ops.jpeg_encode import JpegOptions
 
     return JpegOptions(quality=flags.jpeg_quality, subsampling=flags.jpeg_subsampling)
+
+
+def rectify_model(flags):
+    """The drivers' ``rectify=`` option of --rectify; None when off."""
+    path = getattr(flags, "rectify", "")
+    if not path:
+        return None
+    from ..ops.rectify import load_camera_model
+
+    return load_camera_model(path)
 
 
 def labels_arg(s: str):

@@ -6,7 +6,7 @@ import os
 import sys
 
 from .common import (DATA, add_framework_flags, add_reference_flags, add_track2d_flags, image_files, jpeg_options,
-                     load_params, play_bag, setup_logging, track2d_options)
+                     load_params, play_bag, rectify_model, setup_logging, track2d_options)
 from .engines import engine_2d, export_if_asked, maybe_data_parallel
 
 
@@ -34,6 +34,9 @@ def main(argv=None) -> int:
         if info is not None and flags.publish_compressed:  # every rank stops here, before any serves
             raise SystemExit("--publish-compressed is not available with data-parallel ranks (raw frames travel "
                              "between them); run one process per GPU")
+        if info is not None and flags.rectify:
+            raise SystemExit("--rectify is not available with data-parallel ranks (the sensor's frames travel "
+                             "between them); run one process per GPU")
         if info is not None and not info.is_main:
             engine.serve()
             from ..parallel.dp import shutdown
@@ -47,7 +50,8 @@ def main(argv=None) -> int:
     drv = RosInference(channel, client, engine=engine, params=params, bus=bus, metrics=metrics,
                        queue_size=None if flags.play or flags.image_src == "local" else 1,
                        batch=flags.live_batch, workers=flags.live_workers, compressed=jpeg_options(flags),
-                       tracks_topic=flags.tracks_topic or None, track_options=track2d_options(flags))
+                       tracks_topic=flags.tracks_topic or None, track_options=track2d_options(flags),
+                       rectify=rectify_model(flags))
     if flags.image_src == "local":
         rc = _run_local_images(drv, flags, params)
         export_if_asked(flags, engine)

@@ -7,7 +7,8 @@ window of remote RPCs per micro-batch) instead of one blocking RPC per frame.
 2D: annotated PNGs to ``out_dir/NNNN.png`` and, if ``out_bag`` is given, the
 input image + annotated image + Detection2DArray written to it (the
 reference opened ``output.bag`` but never wrote); with ``compressed=`` the annotated
-image is a JPEG ``CompressedImage`` on ``<pub_topic>/compressed``; with ``tracks_topic=`` the
+image is a JPEG ``CompressedImage`` on ``<pub_topic>/compressed``; with ``rectify=`` every frame is
+rectified from the camera's calibration first, as in the live driver; with ``tracks_topic=`` the
 frames are tracked in bag order and the tracks message is written to that topic.  3D: the input cloud and
 the BoundingBoxArray are written to ``<bag>_output.bag`` like the
 reference.  Bag path and output dir are arguments (fixes A14);

@@ -102,6 +102,21 @@ class Detector2D(ABC):
             trk = self._tracker = Tracker2D(device=getattr(self, "device", None) or "cpu", **options)
         return trk
 
+    def rectifier(self, model):
+        """This engine's :class:`~triton_client_amd.ops.rectify.Rectifier` for the camera model
+        ``model``, made once per model: on the engine's GPU when it has one (``device``;
+        ``tca_rectify``), else — CPU and remote engines — with the host definition."""
+        made = getattr(self, "_rectifiers", None)
+        if made is None:
+            made = self._rectifiers = {}
+        rec = made.get(model)  # (a CameraModel hashes by identity)
+        if rec is None:
+            from ..ops.rectify import Rectifier
+
+            dev = getattr(self, "device", None)
+            rec = made[model] = Rectifier(model, device=dev if str(dev).startswith("cuda") else "cpu")
+        return rec
+
 
 class Detector3D(ABC):
     names: List[str] = []

@@ -19,7 +19,9 @@ camera (:class:`LiveCamera`)
     HIP conversion to rgb8 (``csrc/kernels/encodings.hip``) into the frame buffer
     (``TCA_DEVICE_ENCODINGS=0``: converted on the host instead).  Then the
     captured YOLOv5 / YOLOv4 / Detectron step, and boxes + labels drawn on the resident frames
-    (``csrc/kernels/draw.hip``); the annotated frames and the detections come
+    (``csrc/kernels/draw.hip``); with ``process(..., rectify=Rectifier)`` the frames are
+    rectified from the camera's calibration on the device first (``csrc/kernels/rectify.hip``,
+    the last step before the captured one); the annotated frames and the detections come
     back in one D2H into pinned memory that the published ``Image`` wraps
     without a copy.  With ``process(..., compressed=JpegOptions(...))`` the step
     also encodes the annotated frames (``csrc/kernels/jpeg_encode.hip``) and
@@ -91,13 +93,17 @@ class _CameraEngine:
     graphs and a pool of pinned staging slots."""
 
     def __init__(self, live: "LiveCamera", kind: str, hw: Tuple[int, int], geo, draw: bool, names: Tuple[str, ...],
-                 sample: np.ndarray, compressed=None):
+                 sample: np.ndarray, compressed=None, rectify=None):
         """geo: the :class:`JpegGeometry` of a ``"jpeg"`` engine, (encoding, step, is_bigendian)
         of a ``"raw"`` one, else None.  compressed: :class:`~triton_client_amd.ops.jpeg_encode.JpegOptions`
-        -- the step also encodes the annotated frames, and they leave as ``CompressedImage``."""
+        -- the step also encodes the annotated frames, and they leave as ``CompressedImage``.
+        rectify: a :class:`~triton_client_amd.ops.rectify.Rectifier` on the detector's GPU -- the
+        frames as the sensor sent them land in a buffer of their own (``unrect_dev``), and the last
+        step of ``pre`` rectifies them into the pipeline's frame buffer (``tca_rectify``)."""
         det = live.det
         self.live, self.kind, self.hw, self.draw = live, kind, hw, draw
         self.compressed, self.names, self.jenc, self.warned = compressed, names, None, False
+        self.rectify = rectify
         raw = geo if kind == "raw" else None
         self.geo = geo = geo if kind == "jpeg" else None
         self.B, dev = det.B, det.device
@@ -119,6 +125,9 @@ class _CameraEngine:
             self.jfiles, self.jlens = self.jenc.buffers()
             inputs += [(self, "jfiles"), (self, "jlens")]
         self.ex = StreamExecutor(self._step, inputs, dev, graph=det.graph)
+        if rectify is not None:  # per set, like the frames they become
+            self.unrect_dev = [torch.empty((self.B, H, W, 3), dtype=torch.uint8, device=dev)
+                               for _ in range(self.ex.sets)]
         if raw is not None:
             self.raw_dev = [torch.empty((self.B, self.raw_stride), dtype=torch.uint8, device=dev)
                             for _ in range(self.ex.sets)]
@@ -154,6 +163,17 @@ class _CameraEngine:
             # all B frames, whatever the batch holds: the captured step's grids are fixed
             self.jenc.encode_(self.p.frames, self.jfiles, self.jlens, stream=torch.cuda.current_stream())
         return res
+
+    def _sensor_frames(self, k: int) -> torch.Tensor:
+        """Where set k's frames land as the sensor sent them: the pipeline's frame buffer, or with
+        ``rectify`` the buffer :meth:`_rectify` reads."""
+        return self.ex.inputs[k][0] if self.rectify is None else self.unrect_dev[k]
+
+    def _rectify(self, k: int, n: int) -> None:
+        """The last step of ``pre``: set k's first n sensor frames, rectified, into the pipeline's
+        frame buffer."""
+        if self.rectify is not None:
+            self.rectify.rectify_(self.unrect_dev[k], self.ex.inputs[k][0], n, torch.cuda.current_stream())
 
     # ------------------------------------------------------------------ host staging
     def _stage_jpeg(self, s, datas: List) -> List[int]:
@@ -218,25 +238,27 @@ class _CameraEngine:
 
                 def pre(k):
                     H, W = self.hw
-                    image_to_rgb8(self.raw_dev[k], H, W, self.step, self.enc, self.be, out=self.ex.inputs[k][0], n=n,
+                    image_to_rgb8(self.raw_dev[k], H, W, self.step, self.enc, self.be, out=self._sensor_frames(k), n=n,
                                   stream=torch.cuda.current_stream())
+                    self._rectify(k, n)
             elif self.kind == "jpeg":
                 def copies(k):
                     return [(self.coef_dev[k], s.coef[:n]), (self.q_dev[k], s.q[:n])]
 
                 def pre(k):
                     g, st = self.geo, _native.stream_ptr(torch.cuda.current_stream())
-                    out = self.ex.inputs[k][0]
+                    out = self._sensor_frames(k)
                     _native.call("tca_jpeg_idct", self.coef_dev[k].data_ptr(), self.q_dev[k].data_ptr(),
                                  self.planes.data_ptr(), self.geom_rec.ctypes.data, g.nblocks, g.plane_bytes, n, st)
                     _native.call("tca_jpeg_color", self.planes.data_ptr(), out.data_ptr(), self.geom_rec.ctypes.data,
                                  g.plane_bytes, g.height * g.width * 3, n, st)
                     for i in fb:  # frames the entropy decoder handed to the host decoder
                         out[i].copy_(s.frames[i], non_blocking=True)
+                    self._rectify(k, n)
             else:
                 def copies(k):
-                    return [(self.ex.inputs[k][0], s.frames[:n])]
-                pre = None
+                    return [(self._sensor_frames(k), s.frames[:n])]
+                pre = None if self.rectify is None else (lambda k: self._rectify(k, n))
             if self.jenc is not None:
                 if out_frames is not None:
                     raise ValueError("compressed output has no caller-provided frame buffers")
@@ -285,7 +307,8 @@ class _CameraEngine:
         return out
 
     def _host_file(self, m, dets: np.ndarray, needed: int) -> bytes:
-        """A frame whose file did not fit the device buffer: decoded, drawn and encoded on the host."""
+        """A frame whose file did not fit the device buffer: decoded, rectified (with ``rectify``),
+        drawn and encoded on the host."""
         from ..ops.jpeg_encode import encode_pil
         from ..utils.draw import draw_detections
         if not self.warned:
@@ -293,6 +316,9 @@ class _CameraEngine:
             log.warning("a %dx%d frame needs %d B as JPEG, the device buffer holds %d B per frame: such frames "
                         "are encoded on the host (raise the cap)", self.hw[1], self.hw[0], needed, self.jenc.cap)
         rgb = np.array(self.live.host_rgb(m, self.hw))
+        if self.rectify is not None:  # the detections are in rectified pixels: so is the frame
+            from ..ops.rectify import rectify_numpy
+            rgb = rectify_numpy(np.ascontiguousarray(rgb), self.rectify.map)
         if self.draw:
             draw_detections(rgb, dets, list(self.names) or None, thickness=self.live.thickness)
         return encode_pil(rgb, self.compressed.quality, self.compressed.subsampling)
@@ -358,9 +384,11 @@ class LiveCamera:
         return ("frames", (H, W), None)
 
     compressed_out = True  # process() takes compressed= (the drivers ask before passing it)
+    rectify_in = True      # ... and rectify=
 
-    def _engine(self, key, draw: bool, names: Tuple[str, ...], sample_msg, compressed=None) -> _CameraEngine:
-        k = (key, draw, names) if compressed is None else (key, draw, names, compressed)
+    def _engine(self, key, draw: bool, names: Tuple[str, ...], sample_msg, compressed=None,
+                rectify=None) -> _CameraEngine:
+        k = (key, draw, names, compressed, rectify)
         eng = self.engines.get(k)
         if eng is None:
             with self.lock:
@@ -368,22 +396,39 @@ class LiveCamera:
                 if eng is None:
                     kind, hw, geo = key
                     sample = self.host_rgb(sample_msg, hw) if self.det.calibrate_target is not None else None
-                    eng = self.engines[k] = _CameraEngine(self, kind, hw, geo, draw, names, sample, compressed)
+                    if rectify is not None:
+                        want = self.det.device.index  # (None: the current GPU)
+                        if rectify.map_dev is None or want not in (None, rectify.map_dev.device.index):
+                            raise ValueError(f"rectify: a Rectifier on {self.det.device} (the engine's "
+                                             f"rectifier()), got one on {rectify.device}")
+                        if sample is not None:  # the detector is calibrated on what it will see
+                            from ..ops.rectify import rectify_numpy
+                            sample = rectify_numpy(np.ascontiguousarray(sample), rectify.map)
+                    eng = self.engines[k] = _CameraEngine(self, kind, hw, geo, draw, names, sample, compressed,
+                                                          rectify)
         return eng
 
     def process(self, messages: Sequence, draw: bool = True, names: Optional[Sequence[str]] = None,
-                compressed=None) -> List[tuple]:
+                compressed=None, rectify=None) -> List[tuple]:
         """-> [(Image, dets [n, 6] x1,y1,x2,y2,conf,cls in frame pixels)] in message order.
         compressed: :class:`~triton_client_amd.ops.jpeg_encode.JpegOptions`; the annotated frames are
-        encoded on the device and come back as ``CompressedImage`` (JPEG) instead."""
+        encoded on the device and come back as ``CompressedImage`` (JPEG) instead.
+        rectify: a :class:`~triton_client_amd.ops.rectify.Rectifier` on the detector's GPU
+        (``det.rectifier(model)``); every frame is rectified on the device before the detector sees
+        it, and frame and detections come back in rectified pixels.  ValueError for a frame that is
+        not of the camera model's size."""
         names = tuple(names or ())
         groups: Dict[tuple, List[int]] = {}
         for i, m in enumerate(messages):
             groups.setdefault(self._key(m), []).append(i)
         out: List[Optional[tuple]] = [None] * len(messages)
         B = self.det.B
+        for key in groups:
+            if rectify is not None and tuple(key[1]) != rectify.hw:
+                raise ValueError(f"rectify: frame {key[1][1]}x{key[1][0]}, the camera model is "
+                                 f"{rectify.hw[1]}x{rectify.hw[0]}")
         for key, idx in groups.items():
-            eng = self._engine(key, draw, names, messages[idx[0]], compressed)
+            eng = self._engine(key, draw, names, messages[idx[0]], compressed, rectify)
             for s in range(0, len(idx), B):
                 chunk = idx[s:s + B]
                 for i, r in zip(chunk, eng.run([messages[i] for i in chunk])):

@@ -18,6 +18,16 @@ re-published in ``header.seq`` order (:mod:`.batching`).
 device inside its captured step (``ops/jpeg_encode.py``); every other engine encodes
 the annotated array with PIL on the host.  The data-parallel ring engines refuse it.
 
+``rectify=CameraModel`` (or the path of a ``camera_calibration`` YAML): every frame is
+rectified from the camera's calibration (``ops/rectify.py``) between decode and detector, so
+the annotated frame is the rectified frame and the detections and tracks messages are in
+rectified pixels, the image the calibration's ``projection_matrix`` describes (give that
+matrix to the LiDAR driver's ``--calib`` as ``projection``).  The local GPU engine rectifies
+on the device (``tca_rectify``, the last step before its captured one); every other engine,
+and ``TCA_DEVICE_RECTIFY=0``, through the engine's ``rectifier(model).frames``.  Headers are
+unchanged; a frame that is not of the model's size is a ``ValueError``.  The data-parallel
+ring engines refuse it.
+
 ``tracks_topic``: also publish, per frame and with the frame's header, one more
 ``Detection2DArray`` with the same detections in the same order whose ``results[0].id``
 holds the detection's track id instead of its class (the convention of the 3D tracks
@@ -81,12 +91,19 @@ class RosInference(BaseInference):
                  bus=None, letterbox: bool = False, conf_thres: float = 0.3, draw: bool = True,
                  publish_detections: bool = True, queue_size: Optional[int] = 1, metrics=None, mode: str = "sync",
                  wire: str = "raw", batch: int = 1, workers: int = 1, compressed=None,
-                 tracks_topic: Optional[str] = None, track_options: Optional[dict] = None):
+                 tracks_topic: Optional[str] = None, track_options: Optional[dict] = None, rectify=None):
         super().__init__(channel, client)
         if compressed is not None and not getattr(engine, "compressed_out", True):
             raise ValueError(f"{type(engine).__name__} does not publish compressed frames: the data-parallel ring "
                              "engines move raw frames between ranks; run without --publish-compressed")
+        if rectify is not None and not getattr(engine, "compressed_out", True):
+            raise ValueError(f"{type(engine).__name__} does not rectify frames: the data-parallel ring engines "
+                             "move the sensor's frames between ranks; run without --rectify")
         self.compressed = compressed
+        if rectify is not None:
+            from ..ops.rectify import as_camera_model
+            rectify = as_camera_model(rectify)
+        self.rectify = rectify
         self._params = params or {}
         self.engine = engine or RemoteDetector2D(channel, client, letterbox=letterbox, conf_thres=conf_thres,
                                                  mode=mode, wire=wire)
@@ -99,6 +116,8 @@ class RosInference(BaseInference):
         self.track_options = dict(track_options or {})
         self.batch, self.workers = max(1, batch), max(1, workers)
         self.runner = None
+        if self.rectify is not None:
+            self.rectifier()  # made here, once, before any worker asks for it
 
     # ------------------------------------------------------------------ run
     def start_inference(self, spin: bool = True, timeout: Optional[float] = None):
@@ -174,11 +193,21 @@ class RosInference(BaseInference):
         timer = StageTimer(self.metrics)
         live = self._live()
         if live is not None:  # device path: GPU decode, graph step, GPU annotation, zero-copy Image
+            kw = {}
+            if self.rectify is not None:
+                rec = self.rectifier()
+                if getattr(live, "rectify_in", False) and rec.gpu:
+                    kw["rectify"] = rec  # rectified on the device, between decode and detector
+                else:  # a device path without the step (the remote client's), or TCA_DEVICE_RECTIFY=0
+                    with timer("rectify"):
+                        rgb = rec.frames([decode_image_msg(m) for m in images])
+                        images = [compat.numpy_to_imgmsg(f, "rgb8", header=m.header) for m, f in zip(images, rgb)]
             with timer("device"):
                 if self.compressed is not None and getattr(live, "compressed_out", False):
-                    res = live.process(images, draw=self.draw, names=self.class_names, compressed=self.compressed)
+                    res = live.process(images, draw=self.draw, names=self.class_names, compressed=self.compressed,
+                                       **kw)
                 else:
-                    res = live.process(images, draw=self.draw, names=self.class_names)
+                    res = live.process(images, draw=self.draw, names=self.class_names, **kw)
                     if self.compressed is not None:  # a device path without the encoder (the remote client's)
                         res = [(self._compress(im), d) for im, d in res]
             with timer("messages"):
@@ -190,6 +219,9 @@ class RosInference(BaseInference):
             return out
         with timer("decode"):
             rgb = [decode_image_msg(m) for m in images]
+        if self.rectify is not None:
+            with timer("rectify"):
+                rgb = self.rectifier().frames(rgb)
         gpu_draw = self.draw and hasattr(self.engine, "detect_annotated") and \
             getattr(getattr(self.engine, "device", None), "type", "cpu") == "cuda"
         with timer("detect"):
@@ -218,6 +250,11 @@ class RosInference(BaseInference):
         """The engine's tracker, made with ``track_options`` on first use."""
         fn = getattr(self.engine, "tracker", None)  # (an engine that is no Detector2D subclass)
         return fn(**self.track_options) if fn is not None else Detector2D.tracker(self.engine, **self.track_options)
+
+    def rectifier(self):
+        """The engine's :class:`~triton_client_amd.ops.rectify.Rectifier` of the ``rectify`` model."""
+        fn = getattr(self.engine, "rectifier", None)  # (an engine that is no Detector2D subclass)
+        return fn(self.rectify) if fn is not None else Detector2D.rectifier(self.engine, self.rectify)
 
     def track(self, results: Sequence[tuple]) -> List[tuple]:
         """The ordered stage: ``process`` results of consecutive frames, in published order →
