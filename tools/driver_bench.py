@@ -118,6 +118,10 @@ def main():
                     help="LiDAR side: also publish every cloud as a 16UC1 depth Image of --depth-size pixels under a "
                          "fixed KITTI-like calibration rescaled to that size (RosInference3D depth_topic)")
     ap.add_argument("--depth-size", default="1280x720", metavar="WxH")
+    ap.add_argument("--scan", action="store_true",
+                    help="LiDAR side: also publish every cloud as a LaserScan of --scan-bins rays over the full circle, "
+                         "the other options at their defaults (RosInference3D scan_topic)")
+    ap.add_argument("--scan-bins", type=int, default=360, metavar="N")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -241,19 +245,24 @@ def main():
                              **({"tracks_topic": "/pc_tracks"} if a.tracks else {}),
                              **({"ranged_topic": "/cam_ranged", "camera_detections_topic": "/cam_det",
                                  "calibration": _kitti_like_calibration()} if a.ranged else {}),
-                             **(_depth_arguments(a) if a.depth else {}))
+                             **(_depth_arguments(a) if a.depth else {}),
+                             **(_scan_arguments(a) if a.scan else {}))
         dets = _detection_messages(msgs_in) if a.ranged else None
         ranged = []
         rsub = compat.Subscriber("/cam_ranged", msgs.Detection2DArray, ranged.append, bus=bus) if a.ranged else None
         depth = []
         dsub = compat.Subscriber("/pc_depth", msgs.Image, lambda m: depth.append(len(m.data)), bus=bus) \
             if a.depth else None
+        scans = []
+        ssub = compat.Subscriber("/pc_scan", msgs.LaserScan, lambda m: scans.append(len(m.ranges)), bus=bus) \
+            if a.scan else None
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout,
              side=("/cam_det", dets[:warm]) if dets else None)
         st.sum.clear(), st.n.clear()
         del ranged[:]
         del depth[:]
+        del scans[:]
         n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout,
                          side=("/cam_det", dets[warm:]) if dets else None)
         drv.stop()
@@ -261,6 +270,8 @@ def main():
             rsub.unregister()
         if dsub is not None:
             dsub.unregister()
+        if ssub is not None:
+            ssub.unregister()
         if info is not None:
             eng3.close()
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
@@ -292,6 +303,14 @@ def main():
             out["lidar"]["output"] += f" + depth Image {o.encoding} {o.width}x{o.height} ({kind})"
             out["lidar"]["depth_imager"] = kind
             out["lidar"]["depth"] = {"messages": len(depth), "bytes_per_image": round(sum(depth) / max(1, len(depth)))}
+        if a.scan:
+            from triton_client_amd.inference.engines import Detector3D
+            from triton_client_amd.ops.laser_scan import device_enabled
+            kind = "tca_laser_scan" if Detector3D.laser_scanner(eng3).gpu and device_enabled() else "host definition"
+            print(f"laser scans: {kind}", file=sys.stderr)
+            out["lidar"]["output"] += f" + LaserScan {drv.scan_options.n} rays ({kind})"
+            out["lidar"]["laser_scanner"] = kind
+            out["lidar"]["scan"] = {"messages": len(scans), "rays_per_scan": round(sum(scans) / max(1, len(scans)))}
         if a.tracks:
             trk = drv.tracker()
             ts = trk.state()
@@ -367,6 +386,15 @@ def _depth_arguments(a):
     cal = _kitti_like_calibration()
     P = np.diag([w / 1242.0, h / 375.0, 1.0]) @ cal.P
     return {"depth_topic": "/pc_depth", "depth_options": DepthOptions(w, h), "calibration": Calibration(P, cal.T)}
+
+
+def _scan_arguments(a):
+    """The driver's scan arguments: --scan-bins rays over the full circle, the default options."""
+    import math
+
+    from triton_client_amd.ops.laser_scan import ScanOptions
+
+    return {"scan_topic": "/pc_scan", "scan_options": ScanOptions(angle_increment=2 * math.pi / a.scan_bins)}
 
 
 def _detection_messages(clouds, per_cloud=64):

@@ -88,6 +88,10 @@ _KERNEL_SIGS = {
     # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z, M (host), W, H, encoding (0: 16UC1,
     # 1: 32FC1), scale, min_depth, splat, plane, out, stream (csrc/kernels/depth_image.hip)
     "tca_depth_image": [P, L, P, P, I, I, I, I, I, I, P, I, I, I, F, F, I, P, P, P],
+    # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z, edge table (device float[n + 1]), n,
+    # min_height, max_height, range_min, range_max, empty bits, privatise (1; 0: no LDS bins, measurements), plane,
+    # out, stream (csrc/kernels/laser_scan.hip)
+    "tca_laser_scan": [P, L, P, P, I, I, I, I, I, I, P, I, F, F, F, F, I, I, P, P, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

@@ -5,8 +5,9 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_depth_flags, add_framework_flags, add_range_flags, add_reference_flags, add_track_flags,
-                     bev_view, depth_options, labels_arg, load_params, range_options, setup_logging, track_options)
+from .common import (DATA, add_depth_flags, add_framework_flags, add_range_flags, add_reference_flags, add_scan_flags,
+                     add_track_flags, bev_view, depth_options, labels_arg, load_params, range_options, scan_options,
+                     setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -34,9 +35,12 @@ def parse_args(argv=None):
     p.add_argument("--depth-out", default="", metavar="DIR",
                    help="save every cloud's 16UC1 depth image as the 16-bit greyscale DIR/NNNN.png (the numbering of "
                         "--bev-out)")
+    add_scan_flags(p, "write every cloud as a sensor_msgs/LaserScan (per angular bin the nearest return in the height "
+                      "band; pointcloud_to_laserscan's parameters) to the output bag on this topic")
     flags = p.parse_args(argv)
     flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
     flags.calibration, flags.depth_options = depth_options(flags, p.error)
+    flags.scan_options = scan_options(flags, p.error)
     return flags
 
 
@@ -67,7 +71,8 @@ def main(argv=None) -> int:
                          calibration=flags.calibration, range_options=flags.range_options,
                          range_slop=flags.range_slop, depth_topic=flags.depth_topic or None,
                          depth_options=flags.depth_options, depth_frame_id=flags.depth_frame_id or "",
-                         depth_out=flags.depth_out or None)
+                         depth_out=flags.depth_out or None, scan_topic=flags.scan_topic or None,
+                         scan_options=flags.scan_options, scan_frame_id=flags.scan_frame_id or "")
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

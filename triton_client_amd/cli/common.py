@@ -325,6 +325,78 @@ def depth_options(flags, error=None):
     return cal, opts
 
 
+_SCAN_FLAGS = ("scan_angle", "scan_increment", "scan_height", "scan_range", "scan_no_inf", "scan_inf_epsilon",
+               "scan_time", "scan_frame_id")
+
+
+def add_scan_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--scan-topic and --scan-* (``ops/laser_scan.py``: ``pointcloud_to_laserscan``'s parameters).
+    The option flags default to None so that one given without a topic is seen."""
+    p.add_argument("--scan-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--scan-angle", default=None, metavar="MIN,MAX",
+                   help="the scan's first and last angle in radians, within [-pi, pi] (default the full circle); a pair "
+                        "that starts with a minus sign is written with '=': --scan-angle=-1.57,1.57")
+    p.add_argument("--scan-increment", type=float, default=None, metavar="RAD",
+                   help="angle between two rays in radians (default pi/180; at most 4096 rays)")
+    p.add_argument("--scan-height", default=None, metavar="MIN,MAX",
+                   help="only points with z in this band, in metres in the cloud's frame, count (default -1,1; inf "
+                        "allowed)")
+    p.add_argument("--scan-range", default=None, metavar="MIN,MAX",
+                   help="only returns within these ranges in metres count (default 0.45,100)")
+    p.add_argument("--scan-no-inf", action="store_const", const=True, default=None,
+                   help="a ray without a return reports range_max + --scan-inf-epsilon, not +inf")
+    p.add_argument("--scan-inf-epsilon", type=float, default=None, metavar="M", help="(default 1.0)")
+    p.add_argument("--scan-time", type=float, default=None, metavar="S",
+                   help="the message's scan_time in seconds (default 1/30)")
+    p.add_argument("--scan-frame-id", default=None, metavar="FRAME", help="frame_id of the scans (default: the cloud's)")
+
+
+def scan_options(flags, error=None):
+    """The ``ScanOptions`` of the --scan-* flags, None without --scan-topic.  A --scan-* flag
+    without a topic, a pair that is no ``MIN,MAX`` and an option out of range are usage errors that
+    name the flag: ``error`` (an ``ArgumentParser.error``) is called with the message, else
+    ``ValueError`` is raised."""
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    if not flags.scan_topic:
+        given = [f for f in _SCAN_FLAGS if getattr(flags, f) is not None]
+        if given:
+            fail(f"--{given[0].replace('_', '-')} needs --scan-topic TOPIC")
+        return None
+    from ..ops.laser_scan import ScanOptions
+
+    def pair(flag, text):
+        try:
+            lo, hi = (float(v) for v in text.split(","))
+        except ValueError:
+            fail(f"{flag}: want MIN,MAX, e.g. -1.57,1.57, got {text!r}")
+        return lo, hi
+
+    kw, flag_of = {}, {}
+    for flag, names in (("--scan-angle", ("angle_min", "angle_max")), ("--scan-height", ("min_height", "max_height")),
+                        ("--scan-range", ("range_min", "range_max"))):
+        text = getattr(flags, flag[2:].replace("-", "_"))
+        if text is not None:
+            kw.update(zip(names, pair(flag, text)))
+        flag_of.update({n: flag for n in names})
+    for flag, name in (("--scan-increment", "angle_increment"), ("--scan-inf-epsilon", "inf_epsilon"),
+                       ("--scan-time", "scan_time")):
+        v = getattr(flags, flag[2:].replace("-", "_"))
+        if v is not None:
+            kw[name] = v
+        flag_of[name] = flag
+    if flags.scan_no_inf:
+        kw["use_inf"] = False
+    try:
+        return ScanOptions(**kw)
+    except ValueError as e:
+        field = str(e).split()[0]
+        fail(f"{flag_of.get(field, '--scan-topic')}: {e}")
+
+
 def bev_view(engine, res: float, enabled):
     """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
     range for an engine that does not know its model's) at ``res`` metres per pixel; None

@@ -247,6 +247,23 @@ class Detector3D(ABC):
         pics = Detector3D.depth_imager(self).images(clouds, calibration.M, opts)  # (duck-typed too)
         return [di.depth_message(c, im, opts, frame_id) for c, im in zip(clouds, pics)]
 
+    def laser_scanner(self):
+        """This engine's :class:`~triton_client_amd.ops.laser_scan.LaserScanner`, made once like
+        :meth:`depth_imager` (``tca_laser_scan`` on the engine's GPU, else the host definition)."""
+        from ..ops.laser_scan import LaserScanner
+
+        return Detector3D._made_once(self, "_laser_scanner", LaserScanner)
+
+    def laser_scans(self, clouds: Sequence[msgs.PointCloud2], opts, frame_id: str = "") -> List[msgs.LaserScan]:
+        """Each cloud as a 2D scan: per cloud one ``LaserScan`` (``opts``: a
+        :class:`~triton_client_amd.ops.laser_scan.ScanOptions`) with the cloud's stamp, in frame
+        ``frame_id`` (the cloud's when empty).  Points are the message's own x, y, z: heights and
+        angles are the sensor frame's."""
+        from ..ops import laser_scan as ls
+
+        rows = Detector3D.laser_scanner(self).ranges(clouds, opts)  # (duck-typed too)
+        return [ls.scan_message(c, r, opts, frame_id) for c, r in zip(clouds, rows)]
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

@@ -54,10 +54,19 @@ pixels, with the cloud's stamp and seq, in frame ``depth_frame_id`` (the cloud's
 It is published after the box message of the same cloud, in published order, and rides in the
 prediction as ``pred["depth"]``; every other message keeps its bytes.
 
+``scan_topic`` (with ``scan_options``, a ``ScanOptions`` or a dict of its fields —
+``pointcloud_to_laserscan``'s parameters): the driver also publishes, per cloud, a
+``sensor_msgs/LaserScan`` for 2D navigation (``ops/laser_scan.py``: ``tca_laser_scan`` on an
+engine's GPU): per angular bin the nearest return in the height band, with the cloud's stamp and
+seq, in frame ``scan_frame_id`` (the cloud's when empty).  No calibration is involved.  It is
+published last of the cloud's messages and rides in the prediction as ``pred["scan"]``; every
+other message keeps its bytes.
+
 Whatever is on, one cloud makes one :class:`CloudResult`: the box message, the prediction and
 one field per option above, None where the option is off (or, for ``ranged``, where the cloud
-found no partner).  :data:`SIDE_OUTPUTS` names those fields in the order they are published
-in, after the box message.
+found no partner).  :data:`OUTPUTS` names those fields in the order they are published in, after
+the box message: the perception and visualisation outputs of :data:`SIDE_OUTPUTS`, then the
+navigation outputs of :data:`NAV_OUTPUTS`.
 """
 from __future__ import annotations
 
@@ -134,8 +143,8 @@ def boxes_to_detection3d(pred: dict, idx, header: msgs.Header, ids=None) -> msgs
 
 @dataclasses.dataclass
 class CloudResult:
-    """What the driver made of one cloud.  ``ranged`` and ``depth`` are the objects that also
-    ride in ``pred`` under those keys."""
+    """What the driver made of one cloud.  ``ranged``, ``depth`` and ``scan`` are the objects that
+    also ride in ``pred`` under those keys."""
     boxes: object  # BoundingBoxArray, or Detection3DArray
     pred: dict
     bev: Optional[msgs.Image] = None
@@ -143,12 +152,16 @@ class CloudResult:
     tracks: object = None  # a message of the box message's type
     ranged: Optional[msgs.Detection2DArray] = None
     depth: Optional[msgs.Image] = None
+    scan: Optional[msgs.LaserScan] = None
 
 
 # The side outputs in publishing order: (CloudResult field, message type; None: the box message's).
 # The driver's ``<name>_topic`` attribute holds the topic, None when the option is off.
 SIDE_OUTPUTS = (("bev", msgs.Image), ("points", msgs.PointCloud2), ("tracks", None),
                 ("ranged", msgs.Detection2DArray), ("depth", msgs.Image))
+# What feeds 2D navigation rather than perception: published after the side outputs.
+NAV_OUTPUTS = (("scan", msgs.LaserScan),)
+OUTPUTS = SIDE_OUTPUTS + NAV_OUTPUTS
 
 
 class RosInference3D(BaseInference):
@@ -160,7 +173,8 @@ class RosInference3D(BaseInference):
                  track_options: Optional[dict] = None, ranged_topic: Optional[str] = None,
                  camera_detections_topic: Optional[str] = None, calibration=None,
                  range_options: Optional[dict] = None, range_slop: float = 0.05, depth_topic: Optional[str] = None,
-                 depth_options=None, depth_frame_id: str = ""):
+                 depth_options=None, depth_frame_id: str = "", scan_topic: Optional[str] = None,
+                 scan_options=None, scan_frame_id: str = ""):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -190,11 +204,18 @@ class RosInference3D(BaseInference):
                 raise ValueError("depth_topic needs calibration and depth_options")
             if not isinstance(depth_options, DepthOptions):
                 self.depth_options = DepthOptions(**depth_options)  # a bad option fails here
+        self.scan_topic, self.scan_frame_id = scan_topic or None, scan_frame_id or ""
+        self.scan_options = scan_options
+        if self.scan_topic:
+            from ..ops.laser_scan import ScanOptions
+
+            if not isinstance(scan_options, ScanOptions):
+                self.scan_options = ScanOptions(**(scan_options or {}))  # a bad option fails here
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
         self.sub = self.pub = None
-        self.side_pubs = {}  # the publishers of the side outputs that are on, by SIDE_OUTPUTS name
+        self.side_pubs = {}  # the publishers of the side outputs that are on, by OUTPUTS name
         # batch > 1: the reference's queue of 50 becomes a latest-wins window
         # drained as micro-batches (one engine call per batch), re-published in
         # header.seq order (see .batching)
@@ -206,7 +227,7 @@ class RosInference3D(BaseInference):
         t = msgs.BoundingBoxArray if self.jsk else msgs.Detection3DArray
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
         self.side_pubs = {name: compat.Publisher(self.side_topic(name), mtype or t, queue_size=1, bus=self.bus)
-                          for name, mtype in SIDE_OUTPUTS if self.side_topic(name)}
+                          for name, mtype in OUTPUTS if self.side_topic(name)}
         if self.ranged_topic:
             self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
                                                 self.pairer.push, queue_size=None, bus=self.bus)
@@ -244,7 +265,7 @@ class RosInference3D(BaseInference):
         self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
 
     def side_topic(self, name: str) -> Optional[str]:
-        """The topic of the side output ``name`` of :data:`SIDE_OUTPUTS`, None when it is off."""
+        """The topic of the side output ``name`` of :data:`OUTPUTS`, None when it is off."""
         return getattr(self, name + "_topic")
 
     def _engine(self, name: str, *args, **kw):
@@ -255,9 +276,9 @@ class RosInference3D(BaseInference):
 
     def _publish(self, r: CloudResult) -> None:
         """One cloud's messages: the box message, then every side output it has, in
-        :data:`SIDE_OUTPUTS` order."""
+        :data:`OUTPUTS` order."""
         self.pub.publish(r.boxes)
-        for name, _ in SIDE_OUTPUTS:
+        for name, _ in OUTPUTS:
             m = getattr(r, name)
             if m is not None:
                 self.side_pubs[name].publish(m)
@@ -301,6 +322,9 @@ class RosInference3D(BaseInference):
         if self.depth_topic:
             with timer("depth_image"):
                 self._depth(clouds, out)
+        if self.scan_topic:
+            with timer("laser_scan"):
+                self._scan(clouds, out)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -331,6 +355,13 @@ class RosInference3D(BaseInference):
         res = self._engine("depth_images", clouds, self.calibration, self.depth_options, self.depth_frame_id)
         for r, m in zip(out, res):
             r.depth = r.pred["depth"] = m
+
+    def _scan(self, clouds, out: List[CloudResult]) -> None:
+        """``scan`` and ``pred["scan"]`` of every result: the cloud's LaserScan message.  One call
+        per batch."""
+        res = self._engine("laser_scans", clouds, self.scan_options, self.scan_frame_id)
+        for r, m in zip(out, res):
+            r.scan = r.pred["scan"] = m
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""

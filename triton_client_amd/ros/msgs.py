@@ -142,6 +142,35 @@ class PointCloud2:
     is_dense: bool = False
 
 
+@dataclass(eq=False)
+class LaserScan:
+    """``ranges`` and ``intensities`` are float32: a NumPy ``<f4`` array from the scanner, a list
+    after a bag that stores messages as dicts.  Two scans are equal when their fields are and
+    their arrays hold the same float32 bits."""
+    header: Header = field(default_factory=Header)
+    angle_min: float = 0.0
+    angle_max: float = 0.0
+    angle_increment: float = 0.0
+    time_increment: float = 0.0
+    scan_time: float = 0.0
+    range_min: float = 0.0
+    range_max: float = 0.0
+    ranges: List[float] = field(default_factory=list)
+    intensities: List[float] = field(default_factory=list)
+
+    def __eq__(self, other):
+        if not isinstance(other, LaserScan):
+            return NotImplemented
+        import numpy as np
+
+        def key(m):
+            return tuple(getattr(m, f.name) for f in fields(m)[:-2]) + tuple(
+                np.asarray(a, "<f4").tobytes() for a in (m.ranges, m.intensities))
+        return key(self) == key(other)
+
+    __hash__ = None
+
+
 # ---------------------------------------------------------------- geometry_msgs
 @dataclass
 class Point:
@@ -244,7 +273,7 @@ class Detection3DArray:
 
 MSG_TYPES: Dict[str, type] = {
     "sensor_msgs/Image": Image, "sensor_msgs/CompressedImage": CompressedImage,
-    "sensor_msgs/PointCloud2": PointCloud2, "sensor_msgs/PointField": PointField,
+    "sensor_msgs/PointCloud2": PointCloud2, "sensor_msgs/PointField": PointField, "sensor_msgs/LaserScan": LaserScan,
     "std_msgs/Header": Header, "jsk_recognition_msgs/BoundingBoxArray": BoundingBoxArray,
     "jsk_recognition_msgs/BoundingBox": BoundingBox, "vision_msgs/Detection2DArray": Detection2DArray,
     "vision_msgs/Detection3DArray": Detection3DArray,
@@ -257,6 +286,8 @@ def to_dict(msg: Any) -> Any:
         return {f.name: to_dict(getattr(msg, f.name)) for f in fields(msg)}
     if isinstance(msg, list):
         return [to_dict(m) for m in msg]
+    if type(msg).__module__ == "numpy" and hasattr(msg, "tolist"):  # LaserScan's float32 arrays
+        return msg.tolist()
     return msg
 
 

@@ -47,6 +47,9 @@ DEFS: Dict[str, str] = {
                                "string name\nuint32 offset\nuint8 datatype\nuint32 count"),
     "sensor_msgs/PointCloud2": ("Header header\nuint32 height\nuint32 width\nPointField[] fields\nbool is_bigendian\n"
                                 "uint32 point_step\nuint32 row_step\nuint8[] data\nbool is_dense"),
+    "sensor_msgs/LaserScan": ("Header header\nfloat32 angle_min\nfloat32 angle_max\nfloat32 angle_increment\n"
+                              "float32 time_increment\nfloat32 scan_time\nfloat32 range_min\nfloat32 range_max\n"
+                              "float32[] ranges\nfloat32[] intensities"),
     "jsk_recognition_msgs/BoundingBox": ("Header header\ngeometry_msgs/Pose pose\ngeometry_msgs/Vector3 dimensions\n"
                                          "float32 value\nuint32 label"),
     "jsk_recognition_msgs/BoundingBoxArray": "Header header\nBoundingBox[] boxes",
@@ -67,6 +70,7 @@ DATACLASS = {
     "geometry_msgs/Quaternion": msgs.Quaternion, "geometry_msgs/Pose": msgs.Pose, "geometry_msgs/Pose2D": msgs.Pose2D,
     "sensor_msgs/Image": msgs.Image, "sensor_msgs/CompressedImage": msgs.CompressedImage,
     "sensor_msgs/PointField": msgs.PointField, "sensor_msgs/PointCloud2": msgs.PointCloud2,
+    "sensor_msgs/LaserScan": msgs.LaserScan,
     "jsk_recognition_msgs/BoundingBox": msgs.BoundingBox, "jsk_recognition_msgs/BoundingBoxArray": msgs.BoundingBoxArray,
     "vision_msgs/ObjectHypothesisWithPose": msgs.ObjectHypothesisWithPose,
     "vision_msgs/BoundingBox2D": msgs.BoundingBox2D, "vision_msgs/Detection2D": msgs.Detection2D,
@@ -168,7 +172,15 @@ def _write(buf: bytearray, value: Any, f: Field, parent: str) -> None:
             buf += struct.pack("<I", len(b))
             buf += b
             return
-        items = list(value or [])
+        if f.size is None and f.base in BUILTIN and type(value).__module__ == "numpy":
+            # a NumPy array (LaserScan.ranges) goes out as one block, not element by element
+            import numpy as np
+
+            a = np.ascontiguousarray(value, np.dtype("<" + BUILTIN[f.base])).reshape(-1)
+            buf += struct.pack("<I", a.size)
+            buf += a.tobytes()
+            return
+        items = list(value if value is not None else [])
         if f.size is None:
             buf += struct.pack("<I", len(items))
         elif len(items) != f.size:
@@ -275,6 +287,13 @@ def _read(mv: memoryview, off: int, f: Field):
                 buf[:] = mv[off: off + n]
                 return memoryview(buf), off + n
         return bytes(mv[off: off + n]), off + n
+    if f.base in BUILTIN and f.size is None:  # (LaserScan's float32[]) one block, as it was written
+        import numpy as np
+
+        dt = np.dtype("<" + BUILTIN[f.base])
+        if off + n * dt.itemsize > len(mv):
+            raise ValueError(f"{f.name}: {n} elements do not fit the message")
+        return np.frombuffer(mv, dt, n, off).copy(), off + n * dt.itemsize
     if f.base in BUILTIN:
         fmt = "<%d%s" % (n, BUILTIN[f.base])
         return list(struct.unpack_from(fmt, mv, off)), off + struct.calcsize(fmt)
