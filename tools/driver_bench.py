@@ -122,6 +122,16 @@ def main():
                     help="LiDAR side: also publish every cloud as a LaserScan of --scan-bins rays over the full circle, "
                          "the other options at their defaults (RosInference3D scan_topic)")
     ap.add_argument("--scan-bins", type=int, default=360, metavar="N")
+    ap.add_argument("--ground", action="store_true",
+                    help="LiDAR side: also publish every cloud's obstacle and ground clouds, the sensor height the "
+                         "synthetic sweep's and the other options at their defaults (RosInference3D obstacles_topic and "
+                         "ground_topic)")
+    ap.add_argument("--ground-only", choices=("obstacles", "ground"), default=None,
+                    help="--ground: publish this one of the two clouds alone")
+    ap.add_argument("--ground-copy", choices=("slab", "counted"), default=None,
+                    help="how --ground copies the split clouds back (default: the splitter's own)")
+    ap.add_argument("--ground-recompute", action="store_true",
+                    help="--ground: the scatter computes the classes again instead of reading the saved ones")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -246,7 +256,15 @@ def main():
                              **({"ranged_topic": "/cam_ranged", "camera_detections_topic": "/cam_det",
                                  "calibration": _kitti_like_calibration()} if a.ranged else {}),
                              **(_depth_arguments(a) if a.depth else {}),
-                             **(_scan_arguments(a) if a.scan else {}))
+                             **(_scan_arguments(a) if a.scan else {}),
+                             **({**{k + "_topic": "/pc_" + k for k in ("obstacles", "ground")
+                                    if a.ground_only in (None, k)},
+                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.ground else {}))
+        if a.ground:
+            from triton_client_amd.inference.engines import Detector3D
+            splitter = Detector3D.ground_splitter(eng3)
+            splitter.copy_back = a.ground_copy or splitter.copy_back
+            splitter.saved = not a.ground_recompute
         dets = _detection_messages(msgs_in) if a.ranged else None
         ranged = []
         rsub = compat.Subscriber("/cam_ranged", msgs.Detection2DArray, ranged.append, bus=bus) if a.ranged else None
@@ -256,6 +274,9 @@ def main():
         scans = []
         ssub = compat.Subscriber("/pc_scan", msgs.LaserScan, lambda m: scans.append(len(m.ranges)), bus=bus) \
             if a.scan else None
+        split = {"/pc_obstacles": [], "/pc_ground": []}
+        gsubs = [compat.Subscriber(t, msgs.PointCloud2, lambda m, t=t: split[t].append(m.width), bus=bus)
+                 for t in split] if a.ground else []
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout,
              side=("/cam_det", dets[:warm]) if dets else None)
@@ -263,6 +284,8 @@ def main():
         del ranged[:]
         del depth[:]
         del scans[:]
+        for v in split.values():
+            del v[:]
         n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout,
                          side=("/cam_det", dets[warm:]) if dets else None)
         drv.stop()
@@ -272,6 +295,8 @@ def main():
             dsub.unregister()
         if ssub is not None:
             ssub.unregister()
+        for g in gsubs:
+            g.unregister()
         if info is not None:
             eng3.close()
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
@@ -311,6 +336,15 @@ def main():
             out["lidar"]["output"] += f" + LaserScan {drv.scan_options.n} rays ({kind})"
             out["lidar"]["laser_scanner"] = kind
             out["lidar"]["scan"] = {"messages": len(scans), "rays_per_scan": round(sum(scans) / max(1, len(scans)))}
+        if a.ground:
+            from triton_client_amd.ops.ground import device_enabled
+            kind = "tca_ground_split" if splitter.gpu and device_enabled() else "host definition"
+            print(f"ground split: {kind}", file=sys.stderr)
+            out["lidar"]["output"] += f" + obstacle and ground PointCloud2 ({kind})"
+            out["lidar"]["ground_splitter"] = kind
+            out["lidar"]["ground"] = {"copy_back": splitter.copy_back, "saved_classes": splitter.saved,
+                                      **{t[4:]: {"messages": len(v), "points_per_cloud": round(sum(v) / max(1, len(v)))}
+                                         for t, v in split.items()}}
         if a.tracks:
             trk = drv.tracker()
             ts = trk.state()

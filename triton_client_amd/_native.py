@@ -92,6 +92,11 @@ _KERNEL_SIGS = {
     # min_height, max_height, range_min, range_max, empty bits, privatise (1; 0: no LDS bins, measurements), plane,
     # out, stream (csrc/kernels/laser_scan.hip)
     "tca_laser_scan": [P, L, P, P, I, I, I, I, I, I, P, I, F, F, F, F, I, I, P, P, P],
+    # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z, edge table (device float[S + 1]), S, nr,
+    # float32 cell, float32 range_min, h0, slope_q, noise_q, thick_q, top_q, want (1 obstacles | 2 ground), saved (1;
+    # 0: the scatter computes the classes again), plane, blocks, cls, out, out bytes, counts, stream
+    # (csrc/kernels/ground.hip)
+    "tca_ground_split": [P, L, P, P, I, I, I, I, I, I, P, I, I, F, F, I, I, I, I, I, I, I, P, P, P, P, L, P, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

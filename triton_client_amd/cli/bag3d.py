@@ -5,9 +5,9 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_depth_flags, add_framework_flags, add_range_flags, add_reference_flags, add_scan_flags,
-                     add_track_flags, bev_view, depth_options, labels_arg, load_params, range_options, scan_options,
-                     setup_logging, track_options)
+from .common import (DATA, add_depth_flags, add_framework_flags, add_ground_flags, add_range_flags,
+                     add_reference_flags, add_scan_flags, add_track_flags, bev_view, depth_options, ground_options,
+                     labels_arg, load_params, range_options, scan_options, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -37,10 +37,15 @@ def parse_args(argv=None):
                         "--bev-out)")
     add_scan_flags(p, "write every cloud as a sensor_msgs/LaserScan (per angular bin the nearest return in the height "
                       "band; pointcloud_to_laserscan's parameters) to the output bag on this topic")
+    add_ground_flags(p, "write, per cloud, the input records that stand above the estimated ground (a PointCloud2 with "
+                        "the input's fields, in input order) to the output bag on this topic",
+                     "write, per cloud, the input records at or below the estimated ground to the output bag on this "
+                     "topic")
     flags = p.parse_args(argv)
     flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
     flags.calibration, flags.depth_options = depth_options(flags, p.error)
     flags.scan_options = scan_options(flags, p.error)
+    flags.ground_options = ground_options(flags, p.error)
     return flags
 
 
@@ -72,7 +77,9 @@ def main(argv=None) -> int:
                          range_slop=flags.range_slop, depth_topic=flags.depth_topic or None,
                          depth_options=flags.depth_options, depth_frame_id=flags.depth_frame_id or "",
                          depth_out=flags.depth_out or None, scan_topic=flags.scan_topic or None,
-                         scan_options=flags.scan_options, scan_frame_id=flags.scan_frame_id or "")
+                         scan_options=flags.scan_options, scan_frame_id=flags.scan_frame_id or "",
+                         obstacles_topic=flags.obstacles_topic or None, ground_topic=flags.ground_topic or None,
+                         ground_options=flags.ground_options)
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

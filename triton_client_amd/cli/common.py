@@ -397,6 +397,74 @@ def scan_options(flags, error=None):
         fail(f"{flag_of.get(field, '--scan-topic')}: {e}")
 
 
+_GROUND_FLAGS = (("ground_sectors", "sectors"), ("ground_cell", "cell"), ("ground_range", None),
+                 ("ground_sensor_height", "sensor_height"), ("ground_slope", "max_slope"), ("ground_noise", "noise"),
+                 ("ground_thickness", "thickness"), ("ground_max_height", "max_height"))
+
+
+def add_ground_flags(p: argparse.ArgumentParser, obstacles_help: str, ground_help: str) -> None:
+    """--obstacles-topic, --ground-topic and --ground-* (``ops/ground.py``).  The option flags
+    default to None so that one given without a topic is seen."""
+    p.add_argument("--obstacles-topic", default="", metavar="TOPIC", help=obstacles_help)
+    p.add_argument("--ground-topic", default="", metavar="TOPIC", help=ground_help)
+    p.add_argument("--ground-sectors", type=int, default=None, metavar="N",
+                   help="angular sectors of the polar grid around z (default 360; 1..4096)")
+    p.add_argument("--ground-cell", type=float, default=None, metavar="M",
+                   help="radial width of a grid ring in metres (default 0.5; 0.05..10)")
+    p.add_argument("--ground-range", default=None, metavar="MIN,MAX",
+                   help="only points at these distances from the z axis, in metres, count (default 0,80; at most 512 "
+                        "rings of --ground-cell)")
+    p.add_argument("--ground-sensor-height", type=float, default=None, metavar="M",
+                   help="the ground is expected at z = -M under the sensor (default 1.8)")
+    p.add_argument("--ground-slope", type=float, default=None, metavar="DEG",
+                   help="slope the ground may take from ring to ring, in degrees (default 10; 0..45)")
+    p.add_argument("--ground-noise", type=float, default=None, metavar="M",
+                   help="allowance for measurement noise in metres (default 0.05)")
+    p.add_argument("--ground-thickness", type=float, default=None, metavar="M",
+                   help="how far above the ground estimate a point is still ground (default 0.2)")
+    p.add_argument("--ground-max-height", type=float, default=None, metavar="M",
+                   help="points higher above the ground than this are dropped (default inf)")
+
+
+def ground_options(flags, error=None):
+    """The ``GroundOptions`` of the --ground-* flags, None without --obstacles-topic and
+    --ground-topic.  A --ground-* flag without either topic, a range that is no ``MIN,MAX`` and an
+    option out of range are usage errors that name the flag: ``error`` (an
+    ``ArgumentParser.error``) is called with the message, else ``ValueError`` is raised."""
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    def flag(attr):
+        return "--" + attr.replace("_", "-")
+
+    if not (flags.obstacles_topic or flags.ground_topic):
+        given = [a for a, _ in _GROUND_FLAGS if getattr(flags, a) is not None]
+        if given:
+            fail(f"{flag(given[0])} needs --obstacles-topic TOPIC or --ground-topic TOPIC")
+        return None
+    from ..ops.ground import GroundOptions
+
+    kw, flag_of = {}, {"range_min": "--ground-range", "range_max": "--ground-range"}
+    for attr, name in _GROUND_FLAGS:
+        v = getattr(flags, attr)
+        if name is None:
+            if v is not None:
+                try:
+                    kw["range_min"], kw["range_max"] = (float(t) for t in v.split(","))
+                except ValueError:
+                    fail(f"--ground-range: want MIN,MAX, e.g. 2,60, got {v!r}")
+            continue
+        flag_of[name] = flag(attr)
+        if v is not None:
+            kw[name] = v
+    try:
+        return GroundOptions(**kw)
+    except ValueError as e:
+        fail(f"{flag_of.get(str(e).split()[0], '--ground-topic')}: {e}")
+
+
 def bev_view(engine, res: float, enabled):
     """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
     range for an engine that does not know its model's) at ``res`` metres per pixel; None

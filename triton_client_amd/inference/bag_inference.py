@@ -22,7 +22,7 @@ from typing import Optional
 
 from ..ros.bag import Bag
 from .ros_inference import RosInference
-from .ros_inference3d import OUTPUTS, RosInference3D
+from .ros_inference3d import ALL_OUTPUTS, RosInference3D
 
 
 def _ingest(engine):
@@ -136,7 +136,8 @@ class BagInference3D(RosInference3D):
         written on that topic.  With ``depth_topic`` every cloud's depth image is written on that
         topic; ``depth_out``: a directory where it is also saved as a 16-bit greyscale
         ``NNNN.png`` (``16UC1`` only; the topic defaults to ``<pub_topic>/depth``).  With
-        ``scan_topic`` every cloud's ``LaserScan`` is written on that topic."""
+        ``scan_topic`` every cloud's ``LaserScan`` is written on that topic, with ``obstacles_topic``
+        / ``ground_topic`` its obstacle and ground clouds."""
         if depth_out and not kw.get("depth_topic"):
             kw["depth_topic"] = ((kw.get("params") or {}).get("pub_topic") or "") + "/depth"
         super().__init__(channel, client, **kw)
@@ -186,7 +187,7 @@ class BagInference3D(RosInference3D):
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
                         ob.write(p["pub_topic"], r.boxes)
-                        for name, _ in OUTPUTS:
+                        for name, _ in ALL_OUTPUTS:
                             if getattr(r, name) is not None:
                                 ob.write(self.side_topic(name), getattr(r, name))
                     if self.depth_out:

@@ -264,6 +264,20 @@ class Detector3D(ABC):
         rows = Detector3D.laser_scanner(self).ranges(clouds, opts)  # (duck-typed too)
         return [ls.scan_message(c, r, opts, frame_id) for c, r in zip(clouds, rows)]
 
+    def ground_splitter(self):
+        """This engine's :class:`~triton_client_amd.ops.ground.GroundSplitter`, made once like
+        :meth:`laser_scanner` (``tca_ground_split`` on the engine's GPU, else the host definition)."""
+        from ..ops.ground import GroundSplitter
+
+        return Detector3D._made_once(self, "_ground_splitter", GroundSplitter)
+
+    def split_ground(self, clouds: Sequence[msgs.PointCloud2], opts, want: int = 3) -> List[tuple]:
+        """Each cloud split at its estimated ground: per cloud ``(obstacles message or None, ground
+        message or None)`` (``opts``: a :class:`~triton_client_amd.ops.ground.GroundOptions`;
+        ``want``: 1 obstacles, 2 ground, 3 both).  The kept records are the input's, byte for byte
+        and in input order, with the cloud's header."""
+        return Detector3D.ground_splitter(self).split(clouds, opts, want)  # (duck-typed too)
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

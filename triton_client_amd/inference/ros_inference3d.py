@@ -64,9 +64,10 @@ other message keeps its bytes.
 
 Whatever is on, one cloud makes one :class:`CloudResult`: the box message, the prediction and
 one field per option above, None where the option is off (or, for ``ranged``, where the cloud
-found no partner).  :data:`OUTPUTS` names those fields in the order they are published in, after
-the box message: the perception and visualisation outputs of :data:`SIDE_OUTPUTS`, then the
-navigation outputs of :data:`NAV_OUTPUTS`.
+found no partner).  :data:`ALL_OUTPUTS` names those fields in the order they are published in,
+after the box message: :data:`OUTPUTS` (the perception and visualisation outputs of
+:data:`SIDE_OUTPUTS`, then the navigation outputs of :data:`NAV_OUTPUTS`), then the split clouds of
+:data:`CLOUD_OUTPUTS`.
 """
 from __future__ import annotations
 
@@ -143,8 +144,8 @@ def boxes_to_detection3d(pred: dict, idx, header: msgs.Header, ids=None) -> msgs
 
 @dataclasses.dataclass
 class CloudResult:
-    """What the driver made of one cloud.  ``ranged``, ``depth`` and ``scan`` are the objects that
-    also ride in ``pred`` under those keys."""
+    """What the driver made of one cloud.  ``ranged``, ``depth``, ``scan``, ``obstacles`` and
+    ``ground`` are the objects that also ride in ``pred`` under those keys."""
     boxes: object  # BoundingBoxArray, or Detection3DArray
     pred: dict
     bev: Optional[msgs.Image] = None
@@ -153,6 +154,8 @@ class CloudResult:
     ranged: Optional[msgs.Detection2DArray] = None
     depth: Optional[msgs.Image] = None
     scan: Optional[msgs.LaserScan] = None
+    obstacles: Optional[msgs.PointCloud2] = None
+    ground: Optional[msgs.PointCloud2] = None
 
 
 # The side outputs in publishing order: (CloudResult field, message type; None: the box message's).
@@ -162,6 +165,9 @@ SIDE_OUTPUTS = (("bev", msgs.Image), ("points", msgs.PointCloud2), ("tracks", No
 # What feeds 2D navigation rather than perception: published after the side outputs.
 NAV_OUTPUTS = (("scan", msgs.LaserScan),)
 OUTPUTS = SIDE_OUTPUTS + NAV_OUTPUTS
+# The cloud split at its estimated ground: published after everything else.
+CLOUD_OUTPUTS = (("obstacles", msgs.PointCloud2), ("ground", msgs.PointCloud2))
+ALL_OUTPUTS = OUTPUTS + CLOUD_OUTPUTS  # what the publishers, ``_publish`` and the bag writer loop over
 
 
 class RosInference3D(BaseInference):
@@ -174,7 +180,8 @@ class RosInference3D(BaseInference):
                  camera_detections_topic: Optional[str] = None, calibration=None,
                  range_options: Optional[dict] = None, range_slop: float = 0.05, depth_topic: Optional[str] = None,
                  depth_options=None, depth_frame_id: str = "", scan_topic: Optional[str] = None,
-                 scan_options=None, scan_frame_id: str = ""):
+                 scan_options=None, scan_frame_id: str = "", obstacles_topic: Optional[str] = None,
+                 ground_topic: Optional[str] = None, ground_options=None):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -211,11 +218,18 @@ class RosInference3D(BaseInference):
 
             if not isinstance(scan_options, ScanOptions):
                 self.scan_options = ScanOptions(**(scan_options or {}))  # a bad option fails here
+        self.obstacles_topic, self.ground_topic = obstacles_topic or None, ground_topic or None
+        self.ground_options = ground_options
+        if self.obstacles_topic or self.ground_topic:
+            from ..ops.ground import GroundOptions
+
+            if not isinstance(ground_options, GroundOptions):
+                self.ground_options = GroundOptions(**(ground_options or {}))  # a bad option fails here
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
         self.sub = self.pub = None
-        self.side_pubs = {}  # the publishers of the side outputs that are on, by OUTPUTS name
+        self.side_pubs = {}  # the publishers of the side outputs that are on, by ALL_OUTPUTS name
         # batch > 1: the reference's queue of 50 becomes a latest-wins window
         # drained as micro-batches (one engine call per batch), re-published in
         # header.seq order (see .batching)
@@ -227,7 +241,7 @@ class RosInference3D(BaseInference):
         t = msgs.BoundingBoxArray if self.jsk else msgs.Detection3DArray
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
         self.side_pubs = {name: compat.Publisher(self.side_topic(name), mtype or t, queue_size=1, bus=self.bus)
-                          for name, mtype in OUTPUTS if self.side_topic(name)}
+                          for name, mtype in ALL_OUTPUTS if self.side_topic(name)}
         if self.ranged_topic:
             self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
                                                 self.pairer.push, queue_size=None, bus=self.bus)
@@ -265,7 +279,7 @@ class RosInference3D(BaseInference):
         self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
 
     def side_topic(self, name: str) -> Optional[str]:
-        """The topic of the side output ``name`` of :data:`OUTPUTS`, None when it is off."""
+        """The topic of the side output ``name`` of :data:`ALL_OUTPUTS`, None when it is off."""
         return getattr(self, name + "_topic")
 
     def _engine(self, name: str, *args, **kw):
@@ -276,9 +290,9 @@ class RosInference3D(BaseInference):
 
     def _publish(self, r: CloudResult) -> None:
         """One cloud's messages: the box message, then every side output it has, in
-        :data:`OUTPUTS` order."""
+        :data:`ALL_OUTPUTS` order."""
         self.pub.publish(r.boxes)
-        for name, _ in OUTPUTS:
+        for name, _ in ALL_OUTPUTS:
             m = getattr(r, name)
             if m is not None:
                 self.side_pubs[name].publish(m)
@@ -325,6 +339,9 @@ class RosInference3D(BaseInference):
         if self.scan_topic:
             with timer("laser_scan"):
                 self._scan(clouds, out)
+        if self.obstacles_topic or self.ground_topic:
+            with timer("ground_split"):
+                self._ground(clouds, out)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -362,6 +379,16 @@ class RosInference3D(BaseInference):
         res = self._engine("laser_scans", clouds, self.scan_options, self.scan_frame_id)
         for r, m in zip(out, res):
             r.scan = r.pred["scan"] = m
+
+    def _ground(self, clouds, out: List[CloudResult]) -> None:
+        """``obstacles`` / ``ground`` and ``pred[...]`` of every result, for the topics that are on:
+        the cloud's records above, and at or below, its estimated ground.  One call per batch."""
+        want = (1 if self.obstacles_topic else 0) | (2 if self.ground_topic else 0)
+        for r, (obs, gnd) in zip(out, self._engine("split_ground", clouds, self.ground_options, want)):
+            if obs is not None:
+                r.obstacles = r.pred["obstacles"] = obs
+            if gnd is not None:
+                r.ground = r.pred["ground"] = gnd
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""

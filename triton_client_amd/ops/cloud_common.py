@@ -1,10 +1,11 @@
 """What the ops that read raw ``PointCloud2`` payloads in place share on the host — the point
 labeler (``ops/points_in_boxes.py``, K22), the bird's-eye-view painter (``ops/bev.py``, K23) and
-the camera ranger (``ops/range2d.py``, K26), the depth imager (``ops/depth_image.py``, K27) and the laser
-scanner (``ops/laser_scan.py``, K29): where a cloud's fields lie (:class:`CloudLayout`),
-which of them a kernel can read in place (:func:`fields_f32`), the byte layout of one staged
-batch (:func:`plan_staging`, :func:`fill_staging`: no torch in either), and the device side of
-such an op (:class:`CloudStager`).
+the camera ranger (``ops/range2d.py``, K26), the depth imager (``ops/depth_image.py``, K27), the
+laser scanner (``ops/laser_scan.py``, K29) and the ground splitter (``ops/ground.py``, K30): where
+a cloud's fields lie (:class:`CloudLayout`), which of them a kernel can read in place
+(:func:`fields_f32`), the byte layout of one staged batch (:func:`plan_staging`,
+:func:`fill_staging`: no torch in either), and the device side of such an op
+(:class:`CloudStager`).
 
 One staged batch is one buffer: frame b's records at ``frame_offs[b]`` (16-byte aligned, plus
 ``misalign``), then ``frame_off`` int64 [B], ``frame_n`` int32 [B] and the op's own sections,
@@ -146,9 +147,10 @@ class CloudStager:
     and one synchronize (:meth:`_fetch`), all on that stream; :meth:`_per_cloud` sends each cloud
     to the device or to the definition.  A batch is cut into several launches (:meth:`_parts`)
     by ``CameraRanger``, ``DepthImager`` (``ops/depth_image.py``, K27, whose cut also bounds the
-    key plane) and ``LaserScanner`` (``ops/laser_scan.py``, K29): ``tca_range2d``, ``tca_depth_image``
-    and ``tca_laser_scan`` refuse more than 64 frames or 2^31 record bytes,
-    while ``tca_points_in_boxes`` checks neither (64-bit frame offsets; its int32 point offsets are
+    key plane), ``LaserScanner`` (``ops/laser_scan.py``, K29) and ``GroundSplitter``
+    (``ops/ground.py``, K30, whose cut also bounds the cell plane): ``tca_range2d``,
+    ``tca_depth_image``, ``tca_laser_scan`` and ``tca_ground_split`` refuse more than 64 frames or
+    2^31 record bytes, while ``tca_points_in_boxes`` checks neither (64-bit frame offsets; its int32 point offsets are
     refused in ``prepare``) and ``tca_bev_render`` takes 65535 frames and a 64-bit byte count."""
 
     def __init__(self, device="auto", ws: Optional[Workspace] = None):

@@ -168,13 +168,12 @@ def edge_table(opts: ScanOptions) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------- definition
-def scan_keys_numpy(points, opts: ScanOptions):
-    """The per-point half of the definition → ``(bin [N] int32, valid [N] bool, r [N] float32)``;
-    ``bin`` is -1 where the point has none."""
-    x, y, z = _xyz(points)
-    t = edge_table(opts)
-    n = opts.n
-    h0, h1, r0, r1 = opts.limits
+def pseudo_bins(x, y, t):
+    """The bin rule on float32 ``x``, ``y`` against an edge table ``t`` float32 ``[n + 1]`` →
+    ``(bin [N] int64, has [N] bool)``: ``searchsorted(t, q, "right") - 1`` with ``q == t_n`` in bin
+    ``n - 1``; ``has`` iff ``s`` is finite and non-zero and ``t_0 <= q <= t_n`` (``bin`` means
+    nothing elsewhere).  Shared with the ground splitter's sectors (``ops/ground.py``, K30)."""
+    n = len(t) - 1
     one = np.float32(1)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         s = np.abs(x) + np.abs(y)
@@ -183,6 +182,16 @@ def scan_keys_numpy(points, opts: ScanOptions):
         b = np.searchsorted(t, np.where(ok, q, np.float32(0)), side="right").astype(np.int64) - 1
         b = np.where(q == t[n], n - 1, b)
         has = ok & (q >= t[0]) & (q <= t[n])
+    return b, has
+
+
+def scan_keys_numpy(points, opts: ScanOptions):
+    """The per-point half of the definition → ``(bin [N] int32, valid [N] bool, r [N] float32)``;
+    ``bin`` is -1 where the point has none."""
+    x, y, z = _xyz(points)
+    h0, h1, r0, r1 = opts.limits
+    b, has = pseudo_bins(x, y, edge_table(opts))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         r = np.sqrt(x * x + y * y).astype(np.float32)
         valid = has & (z >= h0) & (z <= h1) & (r >= r0) & (r <= r1)
     return np.where(has, b, -1).astype(np.int32), valid, r
