@@ -95,6 +95,32 @@ def test_dp_device_resident_two_ranks(cuda):
     assert res == {0: "ok", 1: "served 1 1"}, res
 
 
+def test_ring_pinned_or_not_leaves_no_stale_error(cuda):
+    """A platform may refuse to page-lock the ring's mapping (hipHostRegister on a
+    virtual machine's GPU): the ring then stays unpinned, the refusal is not reported by
+    the next framework launch of this thread, and copies through the mapping still work."""
+    import torch
+
+    from triton_client_amd.parallel.host_ring import HostRing
+
+    ring = HostRing(f"tca_test_pin_{os.getpid()}", nslots=2, world=1, create=True, pin=True)
+    try:
+        data = ring.new_generation(1 << 20)
+        assert data.pinned in (True, False)
+        x = torch.arange(16, dtype=torch.uint8, device=cuda)
+        assert int((x + 1).sum()) == 136  # a launch right after the registration
+        slot = data.slot(1)
+        slot[:16] = np.arange(16, dtype=np.uint8)
+        dev = torch.from_numpy(slot[:16]).to(cuda, non_blocking=True)
+        torch.from_numpy(slot[16:32]).copy_(dev + 1, non_blocking=True)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(slot[16:32], np.arange(1, 17, dtype=np.uint8))
+        del slot
+    finally:
+        ring.close()
+    assert not os.path.exists(ring.ctl_path)
+
+
 def _family_worker(rank, world, port, q, family):
     """Every reference family on the device-resident DP path: rank 0's gathered
     detections vs a single-rank run of the same engine on the same inputs."""

@@ -28,6 +28,18 @@ def test_frag_weights_layout_cpu():
         assert wf[ks, g, 0, fq, fr, e] == hi[n, k] and wf[ks, g, 1, fq, fr, e] == lo[n, k]
 
 
+def _refused(cuda, call, out_shape):
+    """A 128-channel tile asked for N % 128 != 0: the launcher refuses the call with an
+    invalid-argument error before any launch, and the output buffer stays as it was."""
+    from triton_client_amd._native import NativeError
+
+    out = torch.full(out_shape, 7.0, dtype=torch.float32, device=cuda)
+    with pytest.raises(NativeError, match="invalid"):
+        call(out)
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()
+
+
 SHAPES = [(2, 23, 31, 64, 128), (1, 21, 37, 256, 256), (2, 19, 50, 64, 64), (3, 9, 16, 96, 128),
           (2, 8, 16, 32, 64), (1, 62, 54, 128, 256)]
 
@@ -41,8 +53,6 @@ def test_hx3_tiles_vs_fp64(cuda, tile, shape):
     outside the output slice stay untouched; and agreement with the halo kernel
     of conv_mfma.hip (tile 90: the same products in another summation order)."""
     B, H, W, cin, cout = shape
-    if tile in (111, 112) and cout % 128:
-        pytest.skip("128-channel tiles need N % 128 == 0")
     torch.manual_seed(tile + cin + cout)
     conv = nn.Conv2d(cin, cout, 3, 1, 1, bias=True).double()
     fc = FusedConv(copy.deepcopy(conv).float(), act=1, device=cuda, precision="fp32")
@@ -51,6 +61,9 @@ def test_hx3_tiles_vs_fp64(cuda, tile, shape):
     res = torch.randn(B, H, W, cout, dtype=torch.float64)
     x = NHWC(to_pairs(buf.float()).to(cuda), 8, cin, pair=True)
     r = NHWC(to_pairs(res.float()).to(cuda), pair=True)
+    if tile in (111, 112) and cout % 128:
+        _refused(cuda, lambda o: fc(x, out=NHWC(o, 8, cout, pair=True), res=r, tile=tile), (B, H, W, cout + 16))
+        return
     outs = {}
     for t in (tile, 90):
         out = torch.full((B, H, W, cout + 16), 7.0, dtype=torch.float32, device=cuda)
@@ -117,8 +130,6 @@ def test_hx3s2_tiles_vs_fp64(cuda, tile, shape):
     fp64, untouched channels outside the output slice, and agreement with the xb
     implicit-GEMM kernel (tile 73) on the same split products."""
     B, H, W, cin, cout = shape
-    if tile in (121, 122) and cout % 128:
-        pytest.skip("128-channel tiles need N % 128 == 0")
     torch.manual_seed(tile + cin + cout + H)
     conv = nn.Conv2d(cin, cout, 3, 2, 1, bias=True).double()
     fc = FusedConv(copy.deepcopy(conv).float(), act=1, device=cuda, precision="fp32")
@@ -128,6 +139,9 @@ def test_hx3s2_tiles_vs_fp64(cuda, tile, shape):
     res = torch.randn(B, Ho, Wo, cout, dtype=torch.float64)
     x = NHWC(to_pairs(buf.float()).to(cuda), 8, cin, pair=True)
     r = NHWC(to_pairs(res.float()).to(cuda), pair=True)
+    if tile in (121, 122) and cout % 128:
+        _refused(cuda, lambda o: fc(x, out=NHWC(o, 8, cout, pair=True), res=r, tile=tile), (B, Ho, Wo, cout + 16))
+        return
     outs = {}
     for t in (tile, 73):
         out = torch.full((B, Ho, Wo, cout + 16), 7.0, dtype=torch.float32, device=cuda)

@@ -283,6 +283,15 @@ def call(name: str, *args) -> None:
     check(fn(*args), name)
 
 
+def clear_error() -> None:
+    """Reset this thread's HIP error state after a failed runtime call that its caller
+    has handled: the runtime keeps the error, and the next launch that asks for the
+    last error (the framework's own launch checks too) would report it as its own."""
+    hip = _load_hip()
+    if hip is not None:
+        hip.hipGetLastError()
+
+
 def _capturing() -> bool:
     from .pipelines.graph import capturing_thread
     return capturing_thread()

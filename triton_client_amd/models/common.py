@@ -177,6 +177,13 @@ def broadcast_parameters(model: nn.Module, src: int = 0) -> None:
 
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         return
+    gloo = dist.get_backend() == "gloo"  # gloo moves host tensors: stage device ones (as FrameExchange does)
     with torch.no_grad():
         for t in list(model.parameters()) + list(model.buffers()):
-            dist.broadcast(t.data, src)
+            if gloo and t.is_cuda:
+                h = t.data.cpu()
+                dist.broadcast(h, src)
+                if dist.get_rank() != src:
+                    t.data.copy_(h)
+            else:
+                dist.broadcast(t.data, src)

@@ -110,13 +110,18 @@ def _open(path: str, size: int, create: bool) -> mmap.mmap:
 
 
 def _host_register(mm: mmap.mmap, size: int) -> bool:
-    """Page-lock a mapping for DMA in this process (hipHostRegister)."""
+    """Page-lock a mapping for DMA in this process (hipHostRegister).  Where the
+    platform cannot page-lock memory the process already has (a virtual machine's
+    GPU, for one) the ring stays unpinned."""
     try:
         import torch
         if not torch.cuda.is_available():
             return False
         addr = ctypes.addressof(ctypes.c_char.from_buffer(mm))
-        return int(torch.cuda.cudart().cudaHostRegister(addr, size, 0)) == 0
+        if int(torch.cuda.cudart().cudaHostRegister(addr, size, 0)) == 0:
+            return True
+        _native.clear_error()  # handled here: not the next launch's error
+        return False
     except Exception:  # noqa: BLE001 - an unpinned ring still works (the copies are staged)
         return False
 

@@ -109,7 +109,13 @@ def _host_register(mm: mmap.mmap, size: int) -> bool:
         if not torch.cuda.is_available():
             return False
         addr = ctypes.addressof(ctypes.c_char.from_buffer(mm))
-        return int(torch.cuda.cudart().cudaHostRegister(addr, size, 0)) == 0
+        if int(torch.cuda.cudart().cudaHostRegister(addr, size, 0)) == 0:
+            return True
+        # a platform that cannot page-lock memory the process already has (a virtual
+        # machine's GPU, for one): handled here, not the next launch's error
+        from .. import _native
+        _native.clear_error()
+        return False
     except Exception:  # noqa: BLE001 - an unpinned region still works (staged copies)
         return False
 
