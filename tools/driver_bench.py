@@ -132,6 +132,11 @@ def main():
                     help="how --ground copies the split clouds back (default: the splitter's own)")
     ap.add_argument("--ground-recompute", action="store_true",
                     help="--ground: the scatter computes the classes again instead of reading the saved ones")
+    ap.add_argument("--clusters", action="store_true",
+                    help="LiDAR side: also publish every cloud's obstacle clusters as a box message, the sensor height "
+                         "the synthetic sweep's and the other options at their defaults (RosInference3D clusters_topic)")
+    ap.add_argument("--clusters-plain", action="store_true",
+                    help="--clusters: one set of atomics per point instead of one per run of a wave (aggregate = 0)")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -259,7 +264,13 @@ def main():
                              **(_scan_arguments(a) if a.scan else {}),
                              **({**{k + "_topic": "/pc_" + k for k in ("obstacles", "ground")
                                     if a.ground_only in (None, k)},
-                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.ground else {}))
+                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.ground else {}),
+                             **({"clusters_topic": "/pc_clusters",
+                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.clusters else {}))
+        if a.clusters:
+            from triton_client_amd.inference.engines import Detector3D
+            extractor = Detector3D.cluster_extractor(eng3)
+            extractor.aggregate = not a.clusters_plain
         if a.ground:
             from triton_client_amd.inference.engines import Detector3D
             splitter = Detector3D.ground_splitter(eng3)
@@ -277,6 +288,9 @@ def main():
         split = {"/pc_obstacles": [], "/pc_ground": []}
         gsubs = [compat.Subscriber(t, msgs.PointCloud2, lambda m, t=t: split[t].append(m.width), bus=bus)
                  for t in split] if a.ground else []
+        boxes = []
+        csub = compat.Subscriber("/pc_clusters", msgs.BoundingBoxArray, lambda m: boxes.append(len(m.boxes)), bus=bus) \
+            if a.clusters else None
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout,
              side=("/cam_det", dets[:warm]) if dets else None)
@@ -284,6 +298,7 @@ def main():
         del ranged[:]
         del depth[:]
         del scans[:]
+        del boxes[:]
         for v in split.values():
             del v[:]
         n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout,
@@ -297,6 +312,8 @@ def main():
             ssub.unregister()
         for g in gsubs:
             g.unregister()
+        if csub is not None:
+            csub.unregister()
         if info is not None:
             eng3.close()
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
@@ -345,6 +362,14 @@ def main():
             out["lidar"]["ground"] = {"copy_back": splitter.copy_back, "saved_classes": splitter.saved,
                                       **{t[4:]: {"messages": len(v), "points_per_cloud": round(sum(v) / max(1, len(v)))}
                                          for t, v in split.items()}}
+        if a.clusters:
+            from triton_client_amd.ops.cluster import device_enabled
+            kind = "tca_cluster" if extractor.gpu and device_enabled() else "host definition"
+            print(f"clusters: {kind}", file=sys.stderr)
+            out["lidar"]["output"] += f" + cluster boxes ({kind})"
+            out["lidar"]["cluster_extractor"] = kind
+            out["lidar"]["clusters"] = {"messages": len(boxes), "aggregate": extractor.aggregate,
+                                        "boxes_per_cloud": round(sum(boxes) / max(1, len(boxes)), 1)}
         if a.tracks:
             trk = drv.tracker()
             ts = trk.state()

@@ -97,6 +97,11 @@ _KERNEL_SIGS = {
     # 0: the scatter computes the classes again), plane, blocks, cls, out, out bytes, counts, stream
     # (csrc/kernels/ground.hip)
     "tca_ground_split": [P, L, P, P, I, I, I, I, I, I, P, I, I, F, F, I, I, I, I, I, I, I, P, P, P, P, L, P, P],
+    # data, data bytes, frame_off, frame_n, frame_n's stride (1; 2: K30's counts, data its output slab), B, max_n,
+    # point_step, off x/y/z, float32 x_min, y_min, cell, W, H, float32 z_min, z_max, min_cell_points, min_points,
+    # max_points, max_clusters, aggregate (1; 0: one set of atomics per point), cnt, lab, pcell, blocks, label, table,
+    # found, err, stream (csrc/kernels/cluster.hip)
+    "tca_cluster": [P, L, P, P, I, I, I, I, I, I, I, F, F, F, I, I, F, F, I, I, I, I, I, P, P, P, P, P, P, P, P, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

@@ -427,8 +427,8 @@ def add_ground_flags(p: argparse.ArgumentParser, obstacles_help: str, ground_hel
 
 
 def ground_options(flags, error=None):
-    """The ``GroundOptions`` of the --ground-* flags, None without --obstacles-topic and
-    --ground-topic.  A --ground-* flag without either topic, a range that is no ``MIN,MAX`` and an
+    """The ``GroundOptions`` of the --ground-* flags, None without --obstacles-topic, --ground-topic
+    and --clusters-topic.  A --ground-* flag without any of them, a range that is no ``MIN,MAX`` and an
     option out of range are usage errors that name the flag: ``error`` (an
     ``ArgumentParser.error``) is called with the message, else ``ValueError`` is raised."""
     def fail(msg):
@@ -439,7 +439,8 @@ def ground_options(flags, error=None):
     def flag(attr):
         return "--" + attr.replace("_", "-")
 
-    if not (flags.obstacles_topic or flags.ground_topic):
+    # (--clusters-topic takes the ground out with the same options)
+    if not (flags.obstacles_topic or flags.ground_topic or getattr(flags, "clusters_topic", "")):
         given = [a for a, _ in _GROUND_FLAGS if getattr(flags, a) is not None]
         if given:
             fail(f"{flag(given[0])} needs --obstacles-topic TOPIC or --ground-topic TOPIC")
@@ -463,6 +464,74 @@ def ground_options(flags, error=None):
         return GroundOptions(**kw)
     except ValueError as e:
         fail(f"{flag_of.get(str(e).split()[0], '--ground-topic')}: {e}")
+
+
+_CLUSTER_FLAGS = (("cluster_cell", "cell"), ("cluster_x_range", "x_range"), ("cluster_y_range", "y_range"),
+                  ("cluster_z_range", "z_range"), ("cluster_min_points", "min_points"),
+                  ("cluster_max_points", "max_points"), ("cluster_min_cell_points", "min_cell_points"),
+                  ("cluster_max", "max_clusters"))
+
+
+def add_cluster_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--clusters-topic and --cluster-* (``ops/cluster.py``).  The option flags default to None so
+    that one given without the topic is seen."""
+    p.add_argument("--clusters-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--cluster-cell", type=float, default=None, metavar="M",
+                   help="side of a grid cell in metres (default 0.4; 0.05..10): points in touching cells are one "
+                        "cluster")
+    for axis, default in (("x", "-80,80"), ("y", "-80,80"), ("z", "-512,512")):
+        p.add_argument(f"--cluster-{axis}-range", default=None, metavar="MIN,MAX",
+                       help=f"only points with {axis} in this range, in metres, count (default {default}; within "
+                            "+-512" + ("" if axis == "z" else ", at most 2048 cells of --cluster-cell") + ")")
+    p.add_argument("--cluster-min-points", type=int, default=None, metavar="N",
+                   help="drop clusters of fewer points (default 5)")
+    p.add_argument("--cluster-max-points", type=int, default=None, metavar="N",
+                   help="drop clusters of more points (default: no limit)")
+    p.add_argument("--cluster-min-cell-points", type=int, default=None, metavar="N",
+                   help="a cell counts as occupied from this many points (default 1)")
+    p.add_argument("--cluster-max", type=int, default=None, metavar="N",
+                   help="report at most this many clusters per cloud (default 1024; 1..4096)")
+    p.add_argument("--cluster-keep-ground", action="store_true",
+                   help="cluster every point of the cloud instead of its obstacle points (the --ground-* flags say "
+                        "how the ground is taken out)")
+
+
+def cluster_options(flags, error=None):
+    """The ``ClusterOptions`` of the --cluster-* flags, None without --clusters-topic.  A --cluster-*
+    flag without the topic, a range that is no ``MIN,MAX`` and an option out of range are usage
+    errors that name the flag, reported like :func:`ground_options`'s."""
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    def flag(attr):
+        return "--" + attr.replace("_", "-")
+
+    if not flags.clusters_topic:
+        given = [a for a, _ in _CLUSTER_FLAGS if getattr(flags, a) is not None]
+        given += ["cluster_keep_ground"] if flags.cluster_keep_ground else []
+        if given:
+            fail(f"{flag(given[0])} needs --clusters-topic TOPIC")
+        return None
+    from ..ops.cluster import ClusterOptions
+
+    kw, flag_of = {"remove_ground": not flags.cluster_keep_ground}, {}
+    for attr, name in _CLUSTER_FLAGS:
+        v = getattr(flags, attr)
+        flag_of[name] = flag(attr)
+        if v is not None and name.endswith("_range"):
+            try:
+                lo, hi = (float(t) for t in v.split(","))
+            except ValueError:
+                fail(f"{flag(attr)}: want MIN,MAX, e.g. -40,40, got {v!r}")
+            v = (lo, hi)
+        if v is not None:
+            kw[name] = v
+    try:
+        return ClusterOptions(**kw)
+    except ValueError as e:
+        fail(f"{flag_of.get(str(e).split()[0], '--clusters-topic')}: {e}")
 
 
 def bev_view(engine, res: float, enabled):

@@ -22,7 +22,7 @@ from typing import Optional
 
 from ..ros.bag import Bag
 from .ros_inference import RosInference
-from .ros_inference3d import ALL_OUTPUTS, RosInference3D
+from .ros_inference3d import PUBLISHED, RosInference3D
 
 
 def _ingest(engine):
@@ -137,7 +137,8 @@ class BagInference3D(RosInference3D):
         topic; ``depth_out``: a directory where it is also saved as a 16-bit greyscale
         ``NNNN.png`` (``16UC1`` only; the topic defaults to ``<pub_topic>/depth``).  With
         ``scan_topic`` every cloud's ``LaserScan`` is written on that topic, with ``obstacles_topic``
-        / ``ground_topic`` its obstacle and ground clouds."""
+        / ``ground_topic`` its obstacle and ground clouds, with ``clusters_topic`` the boxes of its
+        obstacle clusters."""
         if depth_out and not kw.get("depth_topic"):
             kw["depth_topic"] = ((kw.get("params") or {}).get("pub_topic") or "") + "/depth"
         super().__init__(channel, client, **kw)
@@ -187,7 +188,7 @@ class BagInference3D(RosInference3D):
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
                         ob.write(p["pub_topic"], r.boxes)
-                        for name, _ in ALL_OUTPUTS:
+                        for name, _ in PUBLISHED:
                             if getattr(r, name) is not None:
                                 ob.write(self.side_topic(name), getattr(r, name))
                     if self.depth_out:

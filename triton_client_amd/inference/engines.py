@@ -278,6 +278,20 @@ class Detector3D(ABC):
         and in input order, with the cloud's header."""
         return Detector3D.ground_splitter(self).split(clouds, opts, want)  # (duck-typed too)
 
+    def cluster_extractor(self):
+        """This engine's :class:`~triton_client_amd.ops.cluster.ClusterExtractor`, made once like
+        :meth:`ground_splitter` (``tca_cluster`` on the engine's GPU, else the host definition)."""
+        from ..ops.cluster import ClusterExtractor
+
+        return Detector3D._made_once(self, "_cluster_extractor", ClusterExtractor)
+
+    def cluster_obstacles(self, clouds: Sequence[msgs.PointCloud2], opts, ground_opts=None, jsk: bool = True) -> list:
+        """Each cloud's obstacle clusters: per cloud one box message of the driver's type with the
+        cloud's header and one axis-aligned, class-agnostic box per cluster (``opts``: a
+        :class:`~triton_client_amd.ops.cluster.ClusterOptions`; ``ground_opts``: the
+        :class:`~triton_client_amd.ops.ground.GroundOptions` the ground is taken out with)."""
+        return Detector3D.cluster_extractor(self).messages(clouds, opts, ground_opts, jsk)  # (duck-typed too)
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

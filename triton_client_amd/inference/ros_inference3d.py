@@ -62,12 +62,20 @@ seq, in frame ``scan_frame_id`` (the cloud's when empty).  No calibration is inv
 published last of the cloud's messages and rides in the prediction as ``pred["scan"]``; every
 other message keeps its bytes.
 
+``clusters_topic`` (with ``cluster_options``, a ``ClusterOptions`` or a dict of its fields, and
+``ground_options``, which it shares with the split clouds): the driver also publishes, per cloud and
+with the cloud's header, a message of the box message's type with one axis-aligned, class-agnostic
+box per cluster of the cloud's obstacle points (``ops/cluster.py``: ``tca_cluster`` on an engine's
+GPU, behind its own ``tca_ground_split`` launch): ``value`` / ``score`` is the cluster's point
+count, ``label`` / ``id`` its number.  It is published last of the cloud's messages and rides in
+the prediction as ``pred["clusters"]``; every other message keeps its bytes.
+
 Whatever is on, one cloud makes one :class:`CloudResult`: the box message, the prediction and
 one field per option above, None where the option is off (or, for ``ranged``, where the cloud
 found no partner).  :data:`ALL_OUTPUTS` names those fields in the order they are published in,
 after the box message: :data:`OUTPUTS` (the perception and visualisation outputs of
 :data:`SIDE_OUTPUTS`, then the navigation outputs of :data:`NAV_OUTPUTS`), then the split clouds of
-:data:`CLOUD_OUTPUTS`.
+:data:`CLOUD_OUTPUTS`; :data:`PUBLISHED` adds the class-agnostic objects of :data:`OBJECT_OUTPUTS` behind them.
 """
 from __future__ import annotations
 
@@ -144,8 +152,8 @@ def boxes_to_detection3d(pred: dict, idx, header: msgs.Header, ids=None) -> msgs
 
 @dataclasses.dataclass
 class CloudResult:
-    """What the driver made of one cloud.  ``ranged``, ``depth``, ``scan``, ``obstacles`` and
-    ``ground`` are the objects that also ride in ``pred`` under those keys."""
+    """What the driver made of one cloud.  ``ranged``, ``depth``, ``clusters``, ``scan``, ``obstacles``
+    and ``ground`` are the objects that also ride in ``pred`` under those keys."""
     boxes: object  # BoundingBoxArray, or Detection3DArray
     pred: dict
     bev: Optional[msgs.Image] = None
@@ -153,6 +161,7 @@ class CloudResult:
     tracks: object = None  # a message of the box message's type
     ranged: Optional[msgs.Detection2DArray] = None
     depth: Optional[msgs.Image] = None
+    clusters: object = None  # a message of the box message's type
     scan: Optional[msgs.LaserScan] = None
     obstacles: Optional[msgs.PointCloud2] = None
     ground: Optional[msgs.PointCloud2] = None
@@ -167,7 +176,10 @@ NAV_OUTPUTS = (("scan", msgs.LaserScan),)
 OUTPUTS = SIDE_OUTPUTS + NAV_OUTPUTS
 # The cloud split at its estimated ground: published after everything else.
 CLOUD_OUTPUTS = (("obstacles", msgs.PointCloud2), ("ground", msgs.PointCloud2))
-ALL_OUTPUTS = OUTPUTS + CLOUD_OUTPUTS  # what the publishers, ``_publish`` and the bag writer loop over
+ALL_OUTPUTS = OUTPUTS + CLOUD_OUTPUTS
+# The obstacle clusters, one class-agnostic box each: published last.
+OBJECT_OUTPUTS = (("clusters", None),)
+PUBLISHED = ALL_OUTPUTS + OBJECT_OUTPUTS  # what the publishers, ``_publish`` and the bag writer loop over
 
 
 class RosInference3D(BaseInference):
@@ -181,7 +193,8 @@ class RosInference3D(BaseInference):
                  range_options: Optional[dict] = None, range_slop: float = 0.05, depth_topic: Optional[str] = None,
                  depth_options=None, depth_frame_id: str = "", scan_topic: Optional[str] = None,
                  scan_options=None, scan_frame_id: str = "", obstacles_topic: Optional[str] = None,
-                 ground_topic: Optional[str] = None, ground_options=None):
+                 ground_topic: Optional[str] = None, ground_options=None, clusters_topic: Optional[str] = None,
+                 cluster_options=None):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -220,16 +233,22 @@ class RosInference3D(BaseInference):
                 self.scan_options = ScanOptions(**(scan_options or {}))  # a bad option fails here
         self.obstacles_topic, self.ground_topic = obstacles_topic or None, ground_topic or None
         self.ground_options = ground_options
-        if self.obstacles_topic or self.ground_topic:
+        self.clusters_topic, self.cluster_options = clusters_topic or None, cluster_options
+        if self.obstacles_topic or self.ground_topic or self.clusters_topic:
             from ..ops.ground import GroundOptions
 
             if not isinstance(ground_options, GroundOptions):
                 self.ground_options = GroundOptions(**(ground_options or {}))  # a bad option fails here
+        if self.clusters_topic:
+            from ..ops.cluster import ClusterOptions
+
+            if not isinstance(cluster_options, ClusterOptions):
+                self.cluster_options = ClusterOptions(**(cluster_options or {}))  # a bad option fails here
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
         self.sub = self.pub = None
-        self.side_pubs = {}  # the publishers of the side outputs that are on, by ALL_OUTPUTS name
+        self.side_pubs = {}  # the publishers of the side outputs that are on, by PUBLISHED name
         # batch > 1: the reference's queue of 50 becomes a latest-wins window
         # drained as micro-batches (one engine call per batch), re-published in
         # header.seq order (see .batching)
@@ -241,7 +260,7 @@ class RosInference3D(BaseInference):
         t = msgs.BoundingBoxArray if self.jsk else msgs.Detection3DArray
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
         self.side_pubs = {name: compat.Publisher(self.side_topic(name), mtype or t, queue_size=1, bus=self.bus)
-                          for name, mtype in ALL_OUTPUTS if self.side_topic(name)}
+                          for name, mtype in PUBLISHED if self.side_topic(name)}
         if self.ranged_topic:
             self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
                                                 self.pairer.push, queue_size=None, bus=self.bus)
@@ -279,7 +298,7 @@ class RosInference3D(BaseInference):
         self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
 
     def side_topic(self, name: str) -> Optional[str]:
-        """The topic of the side output ``name`` of :data:`ALL_OUTPUTS`, None when it is off."""
+        """The topic of the side output ``name`` of :data:`PUBLISHED`, None when it is off."""
         return getattr(self, name + "_topic")
 
     def _engine(self, name: str, *args, **kw):
@@ -290,9 +309,9 @@ class RosInference3D(BaseInference):
 
     def _publish(self, r: CloudResult) -> None:
         """One cloud's messages: the box message, then every side output it has, in
-        :data:`ALL_OUTPUTS` order."""
+        :data:`PUBLISHED` order."""
         self.pub.publish(r.boxes)
-        for name, _ in ALL_OUTPUTS:
+        for name, _ in PUBLISHED:
             m = getattr(r, name)
             if m is not None:
                 self.side_pubs[name].publish(m)
@@ -342,6 +361,9 @@ class RosInference3D(BaseInference):
         if self.obstacles_topic or self.ground_topic:
             with timer("ground_split"):
                 self._ground(clouds, out)
+        if self.clusters_topic:
+            with timer("cluster"):
+                self._clusters(clouds, out)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -389,6 +411,13 @@ class RosInference3D(BaseInference):
                 r.obstacles = r.pred["obstacles"] = obs
             if gnd is not None:
                 r.ground = r.pred["ground"] = gnd
+
+    def _clusters(self, clouds, out: List[CloudResult]) -> None:
+        """``clusters`` and ``pred["clusters"]`` of every result: the box message of the cloud's
+        obstacle clusters.  One call per batch."""
+        res = self._engine("cluster_obstacles", clouds, self.cluster_options, self.ground_options, self.jsk)
+        for r, m in zip(out, res):
+            r.clusters = r.pred["clusters"] = m
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""

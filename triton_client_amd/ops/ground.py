@@ -373,6 +373,29 @@ def regions_of(host: np.ndarray, c: GroundCall, want: int) -> List[tuple]:
     return res
 
 
+def parts_of(most: int):
+    """The cut of a layout's clouds into launches of at most ``most`` clouds and less than 2^31 staged
+    bytes, as a function of ``(idx, clouds)`` (``ops/cluster.py`` cuts with it too)."""
+    def parts(idx, clouds):
+        part, size = [], 0
+        for i in idx:
+            nb = _align(len(clouds[i].data)) + 16
+            if part and (len(part) == most or size + nb >= INT31):
+                yield part
+                part, size = [], 0
+            part.append(i)
+            size += nb
+        if part:
+            yield part
+
+    return parts
+
+
+def most_clouds(opts: GroundOptions) -> int:
+    """How many clouds of these options fit one launch: 64, and 2^24 cells."""
+    return max(1, min(MAX_FRAMES, MAX_PLANE // (int(opts.sectors) * opts.nr)))
+
+
 class GroundSplitter(CloudStager):
     """Splits clouds into obstacle and ground clouds: on a GPU with ``tca_ground_split`` (its own
     workspace, stream and pinned staging: one H2D of the payloads and the edge table, one launch and
@@ -455,21 +478,7 @@ class GroundSplitter(CloudStager):
     def _parts_for(self, opts: GroundOptions):
         """The cut of a layout's clouds into launches of at most 64 clouds, less than 2^31 staged
         bytes and at most 2^24 cells."""
-        most = max(1, min(MAX_FRAMES, MAX_PLANE // (int(opts.sectors) * opts.nr)))
-
-        def parts(idx, clouds):
-            part, size = [], 0
-            for i in idx:
-                nb = _align(len(clouds[i].data)) + 16
-                if part and (len(part) == most or size + nb >= INT31):
-                    yield part
-                    part, size = [], 0
-                part.append(i)
-                size += nb
-            if part:
-                yield part
-
-        return parts
+        return parts_of(most_clouds(opts))
 
     def _parts(self, idx, clouds, opts: Optional[GroundOptions] = None):
         return self._parts_for(opts or GroundOptions())(idx, clouds)
