@@ -49,6 +49,7 @@
 //
 // Nothing is allocated, no hipMemset is used, only integer atomics.
 #include "tca_cloud_load.h"
+#include "tca_cluster.h"
 #include "tca_common.h"
 
 #include <cmath>
@@ -80,13 +81,6 @@ struct ClusterArgs {
   float x0, y0, c32, z0, z1;
   int min_cell, min_pts, max_pts, max_k;
 };
-
-struct Row {  // 64 bytes: ops/cluster.py TABLE_DTYPE
-  int n, root;
-  int min_x, max_x, min_y, max_y, min_z, max_z;
-  long long sum_x, sum_y, sum_z, pad;
-};
-static_assert(sizeof(Row) == 64, "a table row is 64 bytes");
 
 // ------------------------------------------------------------------------------ union-find
 template <int kScope>
@@ -120,28 +114,6 @@ __device__ __forceinline__ bool uf_unite(int* lab, int a, int b, int bound) {
     b = lo;
   }
   return false;
-}
-
-// ------------------------------------------------------------------------------- wave runs
-// The run of consecutive lanes with this lane's key (key < 0: no run): is the lane its head, its position in
-// the run and the run's length.
-struct Run {
-  bool head;
-  int pos, len;
-};
-
-__device__ __forceinline__ Run wave_run(int key) {
-  const int lane = threadIdx.x & 63;
-  const int prev = __shfl_up(key, 1, 64);
-  Run r;
-  r.head = key >= 0 && (lane == 0 || prev != key);
-  const unsigned long long brk = __ballot(key < 0 || r.head);  // every run starts at a break
-  const unsigned long long after = lane == 63 ? 0ull : (brk >> (lane + 1));
-  const int rest = after ? (__builtin_ctzll(after) + 1) : (64 - lane);  // lanes from this one to the run's end
-  const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-  r.pos = (brk & upto) ? lane - (63 - __builtin_clzll(brk & upto)) : 0;
-  r.len = r.pos + rest;
-  return r;
 }
 
 // ----------------------------------------------------------------------------------- reset

@@ -137,6 +137,9 @@ def main():
                          "the synthetic sweep's and the other options at their defaults (RosInference3D clusters_topic)")
     ap.add_argument("--clusters-plain", action="store_true",
                     help="--clusters: one set of atomics per point instead of one per run of a wave (aggregate = 0)")
+    ap.add_argument("--clusters-oriented", action="store_true",
+                    help="--clusters: fit an oriented box to every cluster, the options at their defaults "
+                         "(RosInference3D cluster_fit)")
     ap.add_argument("--batch", type=int, default=32, help="micro-batch per engine call")
     ap.add_argument("--workers", type=int, default=2, help="driver worker threads (host || device overlap)")
     ap.add_argument("--hw", default="720,1280")
@@ -154,6 +157,8 @@ def main():
     a = ap.parse_args()
     if a.depth and a.ranged:
         ap.error("--depth rescales the calibration that --ranged uses as it is: run them apart")
+    if a.clusters_oriented and not a.clusters:
+        ap.error("--clusters-oriented needs --clusters")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # self-launch (a child: nothing has touched the GPU)
         import socket
         import subprocess
@@ -265,7 +270,7 @@ def main():
                              **({**{k + "_topic": "/pc_" + k for k in ("obstacles", "ground")
                                     if a.ground_only in (None, k)},
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.ground else {}),
-                             **({"clusters_topic": "/pc_clusters",
+                             **({"clusters_topic": "/pc_clusters", "cluster_fit": {} if a.clusters_oriented else None,
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.clusters else {}))
         if a.clusters:
             from triton_client_amd.inference.engines import Detector3D
@@ -368,6 +373,11 @@ def main():
             print(f"clusters: {kind}", file=sys.stderr)
             out["lidar"]["output"] += f" + cluster boxes ({kind})"
             out["lidar"]["cluster_extractor"] = kind
+            if a.clusters_oriented:
+                from triton_client_amd.ops import cluster_fit
+                fit = "tca_cluster_fit" if kind == "tca_cluster" and cluster_fit.device_enabled() else "host definition"
+                print(f"oriented fit: {fit}", file=sys.stderr)
+                out["lidar"]["cluster_fit"] = {"kind": fit, "split": extractor.fit_split}
             out["lidar"]["clusters"] = {"messages": len(boxes), "aggregate": extractor.aggregate,
                                         "boxes_per_cloud": round(sum(boxes) / max(1, len(boxes)), 1)}
         if a.tracks:

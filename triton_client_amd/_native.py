@@ -102,6 +102,11 @@ _KERNEL_SIGS = {
     # max_points, max_clusters, aggregate (1; 0: one set of atomics per point), cnt, lab, pcell, blocks, label, table,
     # found, err, stream (csrc/kernels/cluster.hip)
     "tca_cluster": [P, L, P, P, I, I, I, I, I, I, I, F, F, F, I, I, F, F, I, I, I, I, I, P, P, P, P, P, P, P, P, P],
+    # data, data bytes, frame_off, frame_n, its stride, B, max_n, point_step, off x/y/z (what tca_cluster took), label,
+    # table, found (what it wrote), max_clusters, angles, d0q, trig (HOST int32 [2][angles]), split (1; 0: one workgroup
+    # per cluster whatever its size), plan, grouped, slots, its bytes, work, its bytes, fit, stream
+    # (csrc/kernels/cluster_fit.hip)
+    "tca_cluster_fit": [P, L, P, P, I, I, I, I, I, I, I, P, P, P, I, I, I, P, I, P, P, P, L, P, L, P, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

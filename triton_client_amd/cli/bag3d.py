@@ -6,8 +6,8 @@ import os
 import sys
 
 from .common import (DATA, add_cluster_flags, add_depth_flags, add_framework_flags, add_ground_flags, add_range_flags,
-                     add_reference_flags, add_scan_flags, add_track_flags, bev_view, cluster_options, depth_options,
-                     ground_options,
+                     add_reference_flags, add_scan_flags, add_track_flags, bev_view, cluster_fit_options, cluster_options,
+                     depth_options, ground_options,
                      labels_arg, load_params, range_options, scan_options, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
@@ -42,14 +42,15 @@ def parse_args(argv=None):
                         "the input's fields, in input order) to the output bag on this topic",
                      "write, per cloud, the input records at or below the estimated ground to the output bag on this "
                      "topic")
-    add_cluster_flags(p, "write, per cloud, a box message of the output type with one axis-aligned, class-agnostic "
-                         "box per cluster of its obstacle points to the output bag on this topic")
+    add_cluster_flags(p, "write, per cloud, a box message of the output type with one class-agnostic box per cluster of its "
+                         "obstacle points to the output bag on this topic (axis-aligned; --cluster-oriented: fitted)")
     flags = p.parse_args(argv)
     flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
     flags.calibration, flags.depth_options = depth_options(flags, p.error)
     flags.scan_options = scan_options(flags, p.error)
     flags.ground_options = ground_options(flags, p.error)
     flags.cluster_options = cluster_options(flags, p.error)
+    flags.cluster_fit = cluster_fit_options(flags, p.error)
     return flags
 
 
@@ -84,7 +85,7 @@ def main(argv=None) -> int:
                          scan_options=flags.scan_options, scan_frame_id=flags.scan_frame_id or "",
                          obstacles_topic=flags.obstacles_topic or None, ground_topic=flags.ground_topic or None,
                          ground_options=flags.ground_options, clusters_topic=flags.clusters_topic or None,
-                         cluster_options=flags.cluster_options)
+                         cluster_options=flags.cluster_options, cluster_fit=flags.cluster_fit)
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

@@ -494,6 +494,14 @@ def add_cluster_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
     p.add_argument("--cluster-keep-ground", action="store_true",
                    help="cluster every point of the cloud instead of its obstacle points (the --ground-* flags say "
                         "how the ground is taken out)")
+    p.add_argument("--cluster-oriented", action="store_true",
+                   help="fit an oriented box to every cluster instead of the axis-aligned one: yaw in [0, pi), the "
+                        "long side along it (the search-based L-shape fit, ops/cluster_fit.py)")
+    p.add_argument("--cluster-fit-angles", type=int, default=None, metavar="N",
+                   help="--cluster-oriented: candidate directions over a quarter turn (default 90; 2..128)")
+    p.add_argument("--cluster-fit-d0", type=float, default=None, metavar="M",
+                   help="--cluster-oriented: a point nearer than this to an edge, in metres, counts in full (default "
+                        "0.1; 0.01..1)")
 
 
 def cluster_options(flags, error=None):
@@ -532,6 +540,35 @@ def cluster_options(flags, error=None):
         return ClusterOptions(**kw)
     except ValueError as e:
         fail(f"{flag_of.get(str(e).split()[0], '--clusters-topic')}: {e}")
+
+
+_FIT_FLAGS = (("cluster_fit_angles", "angles"), ("cluster_fit_d0", "d0"))
+
+
+def cluster_fit_options(flags, error=None):
+    """The ``FitOptions`` of --cluster-oriented and the --cluster-fit-* flags, None without
+    --cluster-oriented.  --cluster-oriented without --clusters-topic, a --cluster-fit-* flag without
+    --cluster-oriented and an option out of range are usage errors that name the flag, reported
+    like :func:`cluster_options`'s."""
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    flag_of = {name: "--" + attr.replace("_", "-") for attr, name in _FIT_FLAGS}
+    kw = {name: getattr(flags, attr) for attr, name in _FIT_FLAGS if getattr(flags, attr) is not None}
+    if not flags.cluster_oriented:
+        if kw:
+            fail(f"{flag_of[next(iter(kw))]} needs --cluster-oriented")
+        return None
+    if not flags.clusters_topic:
+        fail("--cluster-oriented needs --clusters-topic TOPIC")
+    from ..ops.cluster_fit import FitOptions
+
+    try:
+        return FitOptions(**kw)
+    except ValueError as e:
+        fail(f"{flag_of.get(str(e).split()[0], '--cluster-oriented')}: {e}")
 
 
 def bev_view(engine, res: float, enabled):

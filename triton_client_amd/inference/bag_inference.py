@@ -138,7 +138,7 @@ class BagInference3D(RosInference3D):
         ``NNNN.png`` (``16UC1`` only; the topic defaults to ``<pub_topic>/depth``).  With
         ``scan_topic`` every cloud's ``LaserScan`` is written on that topic, with ``obstacles_topic``
         / ``ground_topic`` its obstacle and ground clouds, with ``clusters_topic`` the boxes of its
-        obstacle clusters."""
+        obstacle clusters (oriented with ``cluster_fit``)."""
         if depth_out and not kw.get("depth_topic"):
             kw["depth_topic"] = ((kw.get("params") or {}).get("pub_topic") or "") + "/depth"
         super().__init__(channel, client, **kw)

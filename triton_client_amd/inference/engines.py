@@ -285,12 +285,15 @@ class Detector3D(ABC):
 
         return Detector3D._made_once(self, "_cluster_extractor", ClusterExtractor)
 
-    def cluster_obstacles(self, clouds: Sequence[msgs.PointCloud2], opts, ground_opts=None, jsk: bool = True) -> list:
+    def cluster_obstacles(self, clouds: Sequence[msgs.PointCloud2], opts, ground_opts=None, jsk: bool = True,
+                          fit=None) -> list:
         """Each cloud's obstacle clusters: per cloud one box message of the driver's type with the
         cloud's header and one axis-aligned, class-agnostic box per cluster (``opts``: a
         :class:`~triton_client_amd.ops.cluster.ClusterOptions`; ``ground_opts``: the
-        :class:`~triton_client_amd.ops.ground.GroundOptions` the ground is taken out with)."""
-        return Detector3D.cluster_extractor(self).messages(clouds, opts, ground_opts, jsk)  # (duck-typed too)
+        :class:`~triton_client_amd.ops.ground.GroundOptions` the ground is taken out with); with
+        ``fit`` (a :class:`~triton_client_amd.ops.cluster_fit.FitOptions`) the boxes are oriented
+        (``tca_cluster_fit`` behind ``tca_cluster``)."""
+        return Detector3D.cluster_extractor(self).messages(clouds, opts, ground_opts, jsk, fit)  # (duck-typed too)
 
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:

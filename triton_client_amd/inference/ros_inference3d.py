@@ -68,7 +68,10 @@ with the cloud's header, a message of the box message's type with one axis-align
 box per cluster of the cloud's obstacle points (``ops/cluster.py``: ``tca_cluster`` on an engine's
 GPU, behind its own ``tca_ground_split`` launch): ``value`` / ``score`` is the cluster's point
 count, ``label`` / ``id`` its number.  It is published last of the cloud's messages and rides in
-the prediction as ``pred["clusters"]``; every other message keeps its bytes.
+the prediction as ``pred["clusters"]``; every other message keeps its bytes.  With ``cluster_fit`` (a
+``FitOptions``, or a dict of its fields: ``angles``, ``d0``) every box is the oriented one of
+``ops/cluster_fit.py`` instead (``tca_cluster_fit`` behind ``tca_cluster`` on the same stream): yaw in
+[0, pi), the long side along it; without it the message keeps its bytes.
 
 Whatever is on, one cloud makes one :class:`CloudResult`: the box message, the prediction and
 one field per option above, None where the option is off (or, for ``ranged``, where the cloud
@@ -194,7 +197,7 @@ class RosInference3D(BaseInference):
                  depth_options=None, depth_frame_id: str = "", scan_topic: Optional[str] = None,
                  scan_options=None, scan_frame_id: str = "", obstacles_topic: Optional[str] = None,
                  ground_topic: Optional[str] = None, ground_options=None, clusters_topic: Optional[str] = None,
-                 cluster_options=None):
+                 cluster_options=None, cluster_fit=None):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -244,6 +247,13 @@ class RosInference3D(BaseInference):
 
             if not isinstance(cluster_options, ClusterOptions):
                 self.cluster_options = ClusterOptions(**(cluster_options or {}))  # a bad option fails here
+        self.cluster_fit = None
+        if cluster_fit is not None:
+            from ..ops.cluster_fit import as_options
+
+            if not self.clusters_topic:
+                raise ValueError("cluster_fit needs clusters_topic")
+            self.cluster_fit = as_options(cluster_fit)  # a bad option fails here
         self.bus, self.jsk, self.labels, self.score_thresh = bus, jsk, labels, score_thresh
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
@@ -414,8 +424,9 @@ class RosInference3D(BaseInference):
 
     def _clusters(self, clouds, out: List[CloudResult]) -> None:
         """``clusters`` and ``pred["clusters"]`` of every result: the box message of the cloud's
-        obstacle clusters.  One call per batch."""
-        res = self._engine("cluster_obstacles", clouds, self.cluster_options, self.ground_options, self.jsk)
+        obstacle clusters, oriented with ``cluster_fit``.  One call per batch."""
+        fit = {} if self.cluster_fit is None else {"fit": self.cluster_fit}  # (an engine of its own sees today's call)
+        res = self._engine("cluster_obstacles", clouds, self.cluster_options, self.ground_options, self.jsk, **fit)
         for r, m in zip(out, res):
             r.clusters = r.pred["clusters"] = m
 

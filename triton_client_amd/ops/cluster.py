@@ -31,8 +31,9 @@ or ``k >= max_clusters``) and a table of ``min(found, max_clusters)`` rows of 64
 (:data:`TABLE_DTYPE`: the point count, the root, the integer bounds and the integer sums of the
 component's points in units of 1/1024 m).  Nothing depends on the order of the points.
 
-Not here: tf, oriented (L-shape) boxes, tracking the clusters, merging them with the detections, and
-a per-point labelled cluster cloud.
+Oriented (L-shape) boxes are ``ops/cluster_fit.py`` (K32), which runs behind this op on request
+(``fit``).  Not here: tf, tracking the clusters, merging them with the detections, and a per-point
+labelled cluster cloud.
 """
 from __future__ import annotations
 
@@ -397,6 +398,7 @@ class ClusterExtractor(CloudStager):
     one-atomic-set-per-point variant (measurements)."""
 
     aggregate = True
+    fit_split = True  # False: ``tca_cluster_fit`` gives every cluster one workgroup (measurements)
 
     def __init__(self, device="auto", ws=None):
         super().__init__(device, ws)
@@ -439,25 +441,38 @@ class ClusterExtractor(CloudStager):
 
     launch = staticmethod(launch)
 
-    def _run_device(self, payloads, ns, layout, opts, ground, labels):
+    def _run_device(self, payloads, ns, layout, opts, ground, labels, fit=None):
+        from . import cluster_fit as F
+
         with torch.cuda.device(self.device):
             st = self._own_stream()
             c = self.prepare(payloads, ns, layout, opts, ground, st)
             launch(c, st, self.aggregate)
-            if not labels:
+            f = None
+            if fit is not None:  # behind tca_cluster on the same stream: the labels stay on the device
+                f = F.prepare(self, c, fit)
+                F.launch(f, st, self.fit_split)
+            if not labels and f is None:
                 return results_of(self._fetch(c.out, c.head_bytes, st), c, ns, False)
-            nbytes = c.out_bytes
-            pin = self._pinned("_pin_out", nbytes + 8 * c.batch)
-            with torch.cuda.stream(st):
+            nbytes = c.out_bytes if labels else c.head_bytes
+            at_fit = _align(nbytes + 8 * c.batch)
+            pin = self._pinned("_pin_out", at_fit + (f.fit_bytes if f is not None else 0))
+            with torch.cuda.stream(st):  # one fetch: the copies, then one synchronize
                 pin[:nbytes].copy_(c.out[:nbytes], non_blocking=True)
-                if c.ground is not None:  # how many records of each slot are obstacles
+                if labels and c.ground is not None:  # how many records of each slot are obstacles
                     pin[nbytes:nbytes + 8 * c.batch].copy_(c.ground.out[c.ground.slab_bytes:c.ground.out_bytes],
                                                             non_blocking=True)
+                if f is not None:
+                    pin[at_fit:at_fit + f.fit_bytes].copy_(f.fit[:f.fit_bytes], non_blocking=True)
             st.synchronize()
             host = pin.numpy()
-            if c.ground is not None:
+            if labels and c.ground is not None:
                 ns = host[nbytes:nbytes + 8 * c.batch].view("<i4")[::2].tolist()
-            return results_of(host[:nbytes], c, ns, True)
+            res = results_of(host[:nbytes], c, ns, labels)
+            if f is None:
+                return res
+            fits = F.results_of(host[at_fit:at_fit + f.fit_bytes], f, [r[0] for r in res])
+            return [(*r, t) for r, t in zip(res, fits)]
 
     def _parts_for(self, opts: ClusterOptions, ground: Optional[G.GroundOptions]):
         """The cut of a layout's clouds into launches: at most 64 clouds, less than 2^31 staged
@@ -469,22 +484,39 @@ class ClusterExtractor(CloudStager):
 
     # ---------------------------------------------------------------------- API
     def extract(self, clouds: Sequence, opts: ClusterOptions, ground: Optional[G.GroundOptions] = None,
-                labels: bool = True) -> List[tuple]:
+                labels: bool = True, fit=None) -> List[tuple]:
         """Per cloud ``(found, label, table)``, in input order; ``labels`` False: ``label`` is None
-        and is not copied back."""
+        and is not copied back.  ``fit`` (a :class:`~triton_client_amd.ops.cluster_fit.FitOptions`):
+        the oriented fit of every table row as a fourth element (K32: ``tca_cluster_fit`` behind
+        ``tca_cluster``; where that one's definition runs, and with ``TCA_DEVICE_CLUSTER_FIT=0``, the cloud
+        takes both definitions on the host: the fit's reads the points and labels there)."""
+        from . import cluster_fit as F
+
         def on_host(i, lay):
-            found, label, table = cluster_cloud_numpy(clouds[i], opts, ground, lay)
-            return found, label if labels else None, table
+            if fit is None:
+                found, label, table = cluster_cloud_numpy(clouds[i], opts, ground, lay)
+                return found, label if labels else None, table
+            pts = cloud_xyzi(clouds[i], lay)  # the fit's definition reads the points the labels are for
+            if opts.remove_ground:
+                pts = obstacle_rows(pts, ground or G.GroundOptions())
+            found, label, table = cluster_numpy(pts, opts)
+            return found, label if labels else None, table, F.fit_numpy(pts, label, table, fit)
 
         return self._per_cloud(
             clouds, lambda i, lay: G.layout_device_ok(lay), on_host,
-            lambda lay, part: (*cloud_bytes(clouds, part), lay, opts, ground, labels), self._run_device,
+            lambda lay, part: (*cloud_bytes(clouds, part), lay, opts, ground, labels, fit), self._run_device,
             lambda i, lay: f"ClusterExtractor: tca_cluster takes little-endian FLOAT32 x, y, z (got {lay}); such "
                            "clouds are clustered on the host",
-            device=self.gpu and device_enabled(), parts=self._parts_for(opts, ground))
+            device=self.gpu and device_enabled() and (fit is None or F.device_enabled()),
+            parts=self._parts_for(opts, ground))
 
     def messages(self, clouds: Sequence, opts: ClusterOptions, ground: Optional[G.GroundOptions] = None,
-                 jsk: bool = True) -> list:
-        """Per cloud its box message, with the cloud's header."""
-        return [cluster_boxes(table, c.header, jsk)
-                for c, (_, _, table) in zip(clouds, self.extract(clouds, opts, ground, labels=False))]
+                 jsk: bool = True, fit=None) -> list:
+        """Per cloud its box message, with the cloud's header; with ``fit`` the boxes are the oriented
+        ones of ``ops/cluster_fit.py``."""
+        res = self.extract(clouds, opts, ground, labels=False, fit=fit)
+        if fit is None:
+            return [cluster_boxes(table, c.header, jsk) for c, (_, _, table) in zip(clouds, res)]
+        from .cluster_fit import fit_boxes
+
+        return [fit_boxes(r[2], r[3], c.header, jsk, fit) for c, r in zip(clouds, res)]
