@@ -135,6 +135,9 @@ def main():
     ap.add_argument("--clusters", action="store_true",
                     help="LiDAR side: also publish every cloud's obstacle clusters as a box message, the sensor height "
                          "the synthetic sweep's and the other options at their defaults (RosInference3D clusters_topic)")
+    ap.add_argument("--grid", action="store_true",
+                    help="LiDAR side: also publish every cloud as a ray-cast OccupancyGrid, the sensor height the synthetic "
+                         "sweep's and the other options at their defaults (RosInference3D grid_topic)")
     ap.add_argument("--clusters-plain", action="store_true",
                     help="--clusters: one set of atomics per point instead of one per run of a wave (aggregate = 0)")
     ap.add_argument("--clusters-oriented", action="store_true",
@@ -271,7 +274,9 @@ def main():
                                     if a.ground_only in (None, k)},
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.ground else {}),
                              **({"clusters_topic": "/pc_clusters", "cluster_fit": {} if a.clusters_oriented else None,
-                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.clusters else {}))
+                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.clusters else {}),
+                             **({"grid_topic": "/pc_grid",
+                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.grid else {}))
         if a.clusters:
             from triton_client_amd.inference.engines import Detector3D
             extractor = Detector3D.cluster_extractor(eng3)
@@ -296,6 +301,10 @@ def main():
         boxes = []
         csub = compat.Subscriber("/pc_clusters", msgs.BoundingBoxArray, lambda m: boxes.append(len(m.boxes)), bus=bus) \
             if a.clusters else None
+        grids = []
+        osub = compat.Subscriber("/pc_grid", msgs.OccupancyGrid,
+                                 lambda m: grids.append(np.bincount(m.data.view(np.uint8), minlength=256)[[100, 0, 255]]),
+                                 bus=bus) if a.grid else None
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout,
              side=("/cam_det", dets[:warm]) if dets else None)
@@ -304,6 +313,7 @@ def main():
         del depth[:]
         del scans[:]
         del boxes[:]
+        del grids[:]
         for v in split.values():
             del v[:]
         n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout,
@@ -319,6 +329,8 @@ def main():
             g.unregister()
         if csub is not None:
             csub.unregister()
+        if osub is not None:
+            osub.unregister()
         if info is not None:
             eng3.close()
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
@@ -380,6 +392,17 @@ def main():
                 out["lidar"]["cluster_fit"] = {"kind": fit, "split": extractor.fit_split}
             out["lidar"]["clusters"] = {"messages": len(boxes), "aggregate": extractor.aggregate,
                                         "boxes_per_cloud": round(sum(boxes) / max(1, len(boxes)), 1)}
+        if a.grid:
+            from triton_client_amd.inference.engines import Detector3D
+            from triton_client_amd.ops.occupancy_grid import device_enabled
+            kind = "tca_occupancy_grid" if Detector3D.grid_mapper(eng3).gpu and device_enabled() else "host definition"
+            o = drv.grid_options
+            print(f"occupancy grids: {kind}", file=sys.stderr)
+            out["lidar"]["output"] += f" + OccupancyGrid {o.W}x{o.H} ({kind})"
+            out["lidar"]["grid_mapper"] = kind
+            mean = (np.sum(grids, 0) / max(1, len(grids))).round().astype(int).tolist() if grids else [0, 0, 0]
+            out["lidar"]["grid"] = {"messages": len(grids), "occupied_cells": mean[0], "free_cells": mean[1],
+                                    "unknown_cells": mean[2]}
         if a.tracks:
             trk = drv.tracker()
             ts = trk.state()

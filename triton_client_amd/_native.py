@@ -107,6 +107,11 @@ _KERNEL_SIGS = {
     # per cluster whatever its size), plan, grouped, slots, its bytes, work, its bytes, fit, stream
     # (csrc/kernels/cluster_fit.hip)
     "tca_cluster_fit": [P, L, P, P, I, I, I, I, I, I, I, P, P, P, I, I, I, P, I, P, P, P, L, P, L, P, P],
+    # K30's slab, its bytes, frame_off, frame_n, K30's counts, B, max_n, point_step, off x/y/z, edge table (device
+    # float[S + 1]), S, float32 x_min, y_min, cell, W, H, min_points, float32 clear_radius, privatise (1; 0: no LDS
+    # keys), aggregate (1; 0: one atomic per point), stage_keys (0; 1: near / far in LDS in the cell pass), cells, its
+    # bytes, keys, its bytes, out, its bytes, stream (csrc/kernels/occupancy_grid.hip)
+    "tca_occupancy_grid": [P, L, P, P, P, I, I, I, I, I, I, P, I, F, F, F, I, I, I, F, I, I, I, P, L, P, L, P, L, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

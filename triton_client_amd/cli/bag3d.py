@@ -5,9 +5,10 @@ import argparse
 import os
 import sys
 
-from .common import (DATA, add_cluster_flags, add_depth_flags, add_framework_flags, add_ground_flags, add_range_flags,
+from .common import (DATA, add_cluster_flags, add_depth_flags, add_framework_flags, add_grid_flags, add_ground_flags,
+                     add_range_flags,
                      add_reference_flags, add_scan_flags, add_track_flags, bev_view, cluster_fit_options, cluster_options,
-                     depth_options, ground_options,
+                     depth_options, grid_options, ground_options,
                      labels_arg, load_params, range_options, scan_options, setup_logging, track_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
@@ -44,6 +45,9 @@ def parse_args(argv=None):
                      "topic")
     add_cluster_flags(p, "write, per cloud, a box message of the output type with one class-agnostic box per cluster of its "
                          "obstacle points to the output bag on this topic (axis-aligned; --cluster-oriented: fitted)")
+    add_grid_flags(p, "write every cloud as a ray-cast nav_msgs/OccupancyGrid (100 where obstacle returns fell, 0 where a return "
+                      "proves the cell free, -1 elsewhere; the --ground-* flags say how the cloud is split) to the output "
+                      "bag on this topic")
     flags = p.parse_args(argv)
     flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
     flags.calibration, flags.depth_options = depth_options(flags, p.error)
@@ -51,6 +55,7 @@ def parse_args(argv=None):
     flags.ground_options = ground_options(flags, p.error)
     flags.cluster_options = cluster_options(flags, p.error)
     flags.cluster_fit = cluster_fit_options(flags, p.error)
+    flags.grid_options = grid_options(flags, p.error)
     return flags
 
 
@@ -85,7 +90,9 @@ def main(argv=None) -> int:
                          scan_options=flags.scan_options, scan_frame_id=flags.scan_frame_id or "",
                          obstacles_topic=flags.obstacles_topic or None, ground_topic=flags.ground_topic or None,
                          ground_options=flags.ground_options, clusters_topic=flags.clusters_topic or None,
-                         cluster_options=flags.cluster_options, cluster_fit=flags.cluster_fit)
+                         cluster_options=flags.cluster_options, cluster_fit=flags.cluster_fit,
+                         grid_topic=flags.grid_topic or None, grid_options=flags.grid_options,
+                         grid_frame_id=flags.grid_frame_id or "")
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

@@ -439,8 +439,9 @@ def ground_options(flags, error=None):
     def flag(attr):
         return "--" + attr.replace("_", "-")
 
-    # (--clusters-topic takes the ground out with the same options)
-    if not (flags.obstacles_topic or flags.ground_topic or getattr(flags, "clusters_topic", "")):
+    # (--clusters-topic and --grid-topic split the cloud with the same options)
+    if not (flags.obstacles_topic or flags.ground_topic or getattr(flags, "clusters_topic", "")
+            or getattr(flags, "grid_topic", "")):
         given = [a for a, _ in _GROUND_FLAGS if getattr(flags, a) is not None]
         if given:
             fail(f"{flag(given[0])} needs --obstacles-topic TOPIC or --ground-topic TOPIC")
@@ -569,6 +570,68 @@ def cluster_fit_options(flags, error=None):
         return FitOptions(**kw)
     except ValueError as e:
         fail(f"{flag_of.get(str(e).split()[0], '--cluster-oriented')}: {e}")
+
+
+_GRID_FLAGS = (("grid_cell", "cell"), ("grid_x_range", "x_range"), ("grid_y_range", "y_range"),
+               ("grid_sectors", "sectors"), ("grid_min_points", "min_points"), ("grid_clear_radius", "clear_radius"))
+
+
+def add_grid_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--grid-topic and --grid-* (``ops/occupancy_grid.py``).  The option flags default to None so
+    that one given without the topic is seen."""
+    p.add_argument("--grid-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--grid-cell", type=float, default=None, metavar="M",
+                   help="side of a grid cell in metres (default 0.2; 0.05..10)")
+    for axis in ("x", "y"):
+        p.add_argument(f"--grid-{axis}-range", default=None, metavar="MIN,MAX",
+                       help=f"the grid's extent in {axis}, in metres (default -40,40; within +-512, at most 2048 cells "
+                            "of --grid-cell)")
+    p.add_argument("--grid-sectors", type=int, default=None, metavar="N",
+                   help="angular sectors the rays are cast in (default 720; 1..4096)")
+    p.add_argument("--grid-min-points", type=int, default=None, metavar="N",
+                   help="a cell is occupied from this many obstacle points (default 1)")
+    p.add_argument("--grid-clear-radius", type=float, default=None, metavar="M",
+                   help="cells whose centre is nearer to the sensor than this are free: the vehicle's own footprint "
+                        "(default 0)")
+    p.add_argument("--grid-frame-id", default=None, metavar="FRAME",
+                   help="frame_id of the grid messages (default: the cloud's)")
+
+
+def grid_options(flags, error=None):
+    """The ``GridOptions`` of the --grid-* flags, None without --grid-topic.  A --grid-* flag without
+    the topic, a range that is no ``MIN,MAX`` and an option out of range are usage errors that name
+    the flag, reported like :func:`cluster_options`'s."""
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    def flag(attr):
+        return "--" + attr.replace("_", "-")
+
+    if not flags.grid_topic:
+        given = [a for a, _ in _GRID_FLAGS + (("grid_frame_id", None),) if getattr(flags, a) is not None]
+        if given:
+            fail(f"{flag(given[0])} needs --grid-topic TOPIC")
+        return None
+    from ..ops.occupancy_grid import GridOptions
+
+    kw, flag_of = {}, {}
+    for attr, name in _GRID_FLAGS:
+        v = getattr(flags, attr)
+        flag_of[name] = flag(attr)
+        if v is not None and name.endswith("_range"):
+            try:
+                lo, hi = (float(t) for t in v.split(","))
+            except ValueError:
+                fail(f"{flag(attr)}: want MIN,MAX, e.g. -40,40, got {v!r}")
+            v = (lo, hi)
+        if v is not None:
+            kw[name] = v
+    try:
+        return GridOptions(**kw)
+    except ValueError as e:
+        fail(f"{flag_of.get(str(e).split()[0], '--grid-topic')}: {e}")
 
 
 def bev_view(engine, res: float, enabled):

@@ -295,6 +295,21 @@ class Detector3D(ABC):
         (``tca_cluster_fit`` behind ``tca_cluster``)."""
         return Detector3D.cluster_extractor(self).messages(clouds, opts, ground_opts, jsk, fit)  # (duck-typed too)
 
+    def grid_mapper(self):
+        """This engine's :class:`~triton_client_amd.ops.occupancy_grid.GridMapper`, made once like
+        :meth:`laser_scanner` (``tca_occupancy_grid`` on the engine's GPU, else the host definition)."""
+        from ..ops.occupancy_grid import GridMapper
+
+        return Detector3D._made_once(self, "_grid_mapper", GridMapper)
+
+    def occupancy_grids(self, clouds: Sequence[msgs.PointCloud2], opts, ground=None,
+                        frame_id: str = "") -> List[msgs.OccupancyGrid]:
+        """Each cloud as a ray-cast occupancy grid: per cloud one ``OccupancyGrid`` (``opts``: a
+        :class:`~triton_client_amd.ops.occupancy_grid.GridOptions`; ``ground``: the
+        :class:`~triton_client_amd.ops.ground.GroundOptions` the cloud is split with) with the
+        cloud's stamp, in frame ``frame_id`` (the cloud's when empty)."""
+        return Detector3D.grid_mapper(self).messages(clouds, opts, ground, frame_id)  # (duck-typed too)
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

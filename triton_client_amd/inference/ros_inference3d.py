@@ -73,6 +73,15 @@ the prediction as ``pred["clusters"]``; every other message keeps its bytes.  Wi
 ``ops/cluster_fit.py`` instead (``tca_cluster_fit`` behind ``tca_cluster`` on the same stream): yaw in
 [0, pi), the long side along it; without it the message keeps its bytes.
 
+``grid_topic`` (with ``grid_options``, a ``GridOptions`` or a dict of its fields, and
+``ground_options``): the driver also publishes, per cloud, a ray-cast ``nav_msgs/OccupancyGrid``
+(``ops/occupancy_grid.py``: ``tca_occupancy_grid`` on an engine's GPU, behind its own
+``tca_ground_split`` launch): 100 where obstacle returns fell, 0 where a return proves the cell
+free, -1 elsewhere, with the cloud's stamp and seq, in frame ``grid_frame_id`` (the cloud's when
+empty).  It is published last of the cloud's messages (:data:`MAP_OUTPUTS`;
+:data:`EVERY_OUTPUT` is what the publishers loop over) and rides in the prediction as
+``pred["grid"]``; every other message keeps its bytes.
+
 Whatever is on, one cloud makes one :class:`CloudResult`: the box message, the prediction and
 one field per option above, None where the option is off (or, for ``ranged``, where the cloud
 found no partner).  :data:`ALL_OUTPUTS` names those fields in the order they are published in,
@@ -155,8 +164,8 @@ def boxes_to_detection3d(pred: dict, idx, header: msgs.Header, ids=None) -> msgs
 
 @dataclasses.dataclass
 class CloudResult:
-    """What the driver made of one cloud.  ``ranged``, ``depth``, ``clusters``, ``scan``, ``obstacles``
-    and ``ground`` are the objects that also ride in ``pred`` under those keys."""
+    """What the driver made of one cloud.  ``ranged``, ``depth``, ``grid``, ``clusters``, ``scan``,
+    ``obstacles`` and ``ground`` are the objects that also ride in ``pred`` under those keys."""
     boxes: object  # BoundingBoxArray, or Detection3DArray
     pred: dict
     bev: Optional[msgs.Image] = None
@@ -164,6 +173,7 @@ class CloudResult:
     tracks: object = None  # a message of the box message's type
     ranged: Optional[msgs.Detection2DArray] = None
     depth: Optional[msgs.Image] = None
+    grid: Optional[msgs.OccupancyGrid] = None
     clusters: object = None  # a message of the box message's type
     scan: Optional[msgs.LaserScan] = None
     obstacles: Optional[msgs.PointCloud2] = None
@@ -182,7 +192,10 @@ CLOUD_OUTPUTS = (("obstacles", msgs.PointCloud2), ("ground", msgs.PointCloud2))
 ALL_OUTPUTS = OUTPUTS + CLOUD_OUTPUTS
 # The obstacle clusters, one class-agnostic box each: published last.
 OBJECT_OUTPUTS = (("clusters", None),)
-PUBLISHED = ALL_OUTPUTS + OBJECT_OUTPUTS  # what the publishers, ``_publish`` and the bag writer loop over
+PUBLISHED = ALL_OUTPUTS + OBJECT_OUTPUTS
+# The maps a planner reads: published last of all.
+MAP_OUTPUTS = (("grid", msgs.OccupancyGrid),)
+EVERY_OUTPUT = PUBLISHED + MAP_OUTPUTS  # what the publishers, ``_publish`` and the bag writer loop over
 
 
 class RosInference3D(BaseInference):
@@ -197,7 +210,8 @@ class RosInference3D(BaseInference):
                  depth_options=None, depth_frame_id: str = "", scan_topic: Optional[str] = None,
                  scan_options=None, scan_frame_id: str = "", obstacles_topic: Optional[str] = None,
                  ground_topic: Optional[str] = None, ground_options=None, clusters_topic: Optional[str] = None,
-                 cluster_options=None, cluster_fit=None):
+                 cluster_options=None, cluster_fit=None, grid_topic: Optional[str] = None, grid_options=None,
+                 grid_frame_id: str = ""):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -237,7 +251,9 @@ class RosInference3D(BaseInference):
         self.obstacles_topic, self.ground_topic = obstacles_topic or None, ground_topic or None
         self.ground_options = ground_options
         self.clusters_topic, self.cluster_options = clusters_topic or None, cluster_options
-        if self.obstacles_topic or self.ground_topic or self.clusters_topic:
+        self.grid_topic, self.grid_frame_id = grid_topic or None, grid_frame_id or ""
+        self.grid_options = grid_options
+        if self.obstacles_topic or self.ground_topic or self.clusters_topic or self.grid_topic:
             from ..ops.ground import GroundOptions
 
             if not isinstance(ground_options, GroundOptions):
@@ -247,6 +263,11 @@ class RosInference3D(BaseInference):
 
             if not isinstance(cluster_options, ClusterOptions):
                 self.cluster_options = ClusterOptions(**(cluster_options or {}))  # a bad option fails here
+        if self.grid_topic:
+            from ..ops.occupancy_grid import GridOptions
+
+            if not isinstance(grid_options, GridOptions):
+                self.grid_options = GridOptions(**(grid_options or {}))  # a bad option fails here
         self.cluster_fit = None
         if cluster_fit is not None:
             from ..ops.cluster_fit import as_options
@@ -258,7 +279,7 @@ class RosInference3D(BaseInference):
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
         self.sub = self.pub = None
-        self.side_pubs = {}  # the publishers of the side outputs that are on, by PUBLISHED name
+        self.side_pubs = {}  # the publishers of the side outputs that are on, by EVERY_OUTPUT name
         # batch > 1: the reference's queue of 50 becomes a latest-wins window
         # drained as micro-batches (one engine call per batch), re-published in
         # header.seq order (see .batching)
@@ -270,7 +291,7 @@ class RosInference3D(BaseInference):
         t = msgs.BoundingBoxArray if self.jsk else msgs.Detection3DArray
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
         self.side_pubs = {name: compat.Publisher(self.side_topic(name), mtype or t, queue_size=1, bus=self.bus)
-                          for name, mtype in PUBLISHED if self.side_topic(name)}
+                          for name, mtype in EVERY_OUTPUT if self.side_topic(name)}
         if self.ranged_topic:
             self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
                                                 self.pairer.push, queue_size=None, bus=self.bus)
@@ -308,7 +329,7 @@ class RosInference3D(BaseInference):
         self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
 
     def side_topic(self, name: str) -> Optional[str]:
-        """The topic of the side output ``name`` of :data:`PUBLISHED`, None when it is off."""
+        """The topic of the side output ``name`` of :data:`EVERY_OUTPUT`, None when it is off."""
         return getattr(self, name + "_topic")
 
     def _engine(self, name: str, *args, **kw):
@@ -319,9 +340,9 @@ class RosInference3D(BaseInference):
 
     def _publish(self, r: CloudResult) -> None:
         """One cloud's messages: the box message, then every side output it has, in
-        :data:`PUBLISHED` order."""
+        :data:`EVERY_OUTPUT` order."""
         self.pub.publish(r.boxes)
-        for name, _ in PUBLISHED:
+        for name, _ in EVERY_OUTPUT:
             m = getattr(r, name)
             if m is not None:
                 self.side_pubs[name].publish(m)
@@ -374,6 +395,9 @@ class RosInference3D(BaseInference):
         if self.clusters_topic:
             with timer("cluster"):
                 self._clusters(clouds, out)
+        if self.grid_topic:
+            with timer("occupancy_grid"):
+                self._grid(clouds, out)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -429,6 +453,13 @@ class RosInference3D(BaseInference):
         res = self._engine("cluster_obstacles", clouds, self.cluster_options, self.ground_options, self.jsk, **fit)
         for r, m in zip(out, res):
             r.clusters = r.pred["clusters"] = m
+
+    def _grid(self, clouds, out: List[CloudResult]) -> None:
+        """``grid`` and ``pred["grid"]`` of every result: the cloud's OccupancyGrid message.  One
+        call per batch."""
+        res = self._engine("occupancy_grids", clouds, self.grid_options, self.ground_options, self.grid_frame_id)
+        for r, m in zip(out, res):
+            r.grid = r.pred["grid"] = m
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""

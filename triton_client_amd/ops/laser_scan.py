@@ -38,8 +38,8 @@ their bits, so an integer minimum does it); nothing depends on the order of the 
 bin holds ``+inf`` (bits ``0x7F800000``), or ``float32(range_max + inf_epsilon)`` with
 ``use_inf`` False.  The output is ``<f4 [n]``.
 
-Not here: ``target_frame`` and tf (the scan is in the cloud's frame), ``intensities`` (left empty,
-as the ROS node leaves them) and ray-cast free space.
+Not here: ``target_frame`` and tf (the scan is in the cloud's frame) and ``intensities`` (left
+empty, as the ROS node leaves them).  Ray-cast free space is ``ops/occupancy_grid.py`` (K33).
 """
 from __future__ import annotations
 

@@ -207,6 +207,36 @@ class Pose2D:
     theta: float = 0.0
 
 
+# ---------------------------------------------------------------- nav_msgs
+@dataclass
+class MapMetaData:
+    map_load_time: Time = field(default_factory=Time)
+    resolution: float = 0.0
+    width: int = 0
+    height: int = 0
+    origin: Pose = field(default_factory=Pose)
+
+
+@dataclass(eq=False)
+class OccupancyGrid:
+    """``data`` is int8, row-major: a NumPy array from the grid mapper, a list after a bag that
+    stores messages as dicts.  Two grids are equal when their fields are and their cells hold the
+    same values."""
+    header: Header = field(default_factory=Header)
+    info: MapMetaData = field(default_factory=MapMetaData)
+    data: List[int] = field(default_factory=list)
+
+    def __eq__(self, other):
+        if not isinstance(other, OccupancyGrid):
+            return NotImplemented
+        import numpy as np
+
+        return (self.header, self.info) == (other.header, other.info) and \
+            np.asarray(self.data, np.int8).tobytes() == np.asarray(other.data, np.int8).tobytes()
+
+    __hash__ = None
+
+
 # ---------------------------------------------------------------- jsk_recognition_msgs
 @dataclass
 class BoundingBox:
@@ -277,6 +307,7 @@ MSG_TYPES: Dict[str, type] = {
     "std_msgs/Header": Header, "jsk_recognition_msgs/BoundingBoxArray": BoundingBoxArray,
     "jsk_recognition_msgs/BoundingBox": BoundingBox, "vision_msgs/Detection2DArray": Detection2DArray,
     "vision_msgs/Detection3DArray": Detection3DArray,
+    "nav_msgs/MapMetaData": MapMetaData, "nav_msgs/OccupancyGrid": OccupancyGrid,
 }
 TYPE_NAMES = {v: k for k, v in MSG_TYPES.items()}
 

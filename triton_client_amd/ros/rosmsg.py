@@ -50,6 +50,9 @@ DEFS: Dict[str, str] = {
     "sensor_msgs/LaserScan": ("Header header\nfloat32 angle_min\nfloat32 angle_max\nfloat32 angle_increment\n"
                               "float32 time_increment\nfloat32 scan_time\nfloat32 range_min\nfloat32 range_max\n"
                               "float32[] ranges\nfloat32[] intensities"),
+    "nav_msgs/MapMetaData": ("time map_load_time\nfloat32 resolution\nuint32 width\nuint32 height\n"
+                             "geometry_msgs/Pose origin"),
+    "nav_msgs/OccupancyGrid": "Header header\nMapMetaData info\nint8[] data",
     "jsk_recognition_msgs/BoundingBox": ("Header header\ngeometry_msgs/Pose pose\ngeometry_msgs/Vector3 dimensions\n"
                                          "float32 value\nuint32 label"),
     "jsk_recognition_msgs/BoundingBoxArray": "Header header\nBoundingBox[] boxes",
@@ -70,7 +73,8 @@ DATACLASS = {
     "geometry_msgs/Quaternion": msgs.Quaternion, "geometry_msgs/Pose": msgs.Pose, "geometry_msgs/Pose2D": msgs.Pose2D,
     "sensor_msgs/Image": msgs.Image, "sensor_msgs/CompressedImage": msgs.CompressedImage,
     "sensor_msgs/PointField": msgs.PointField, "sensor_msgs/PointCloud2": msgs.PointCloud2,
-    "sensor_msgs/LaserScan": msgs.LaserScan,
+    "sensor_msgs/LaserScan": msgs.LaserScan, "nav_msgs/MapMetaData": msgs.MapMetaData,
+    "nav_msgs/OccupancyGrid": msgs.OccupancyGrid,
     "jsk_recognition_msgs/BoundingBox": msgs.BoundingBox, "jsk_recognition_msgs/BoundingBoxArray": msgs.BoundingBoxArray,
     "vision_msgs/ObjectHypothesisWithPose": msgs.ObjectHypothesisWithPose,
     "vision_msgs/BoundingBox2D": msgs.BoundingBox2D, "vision_msgs/Detection2D": msgs.Detection2D,
