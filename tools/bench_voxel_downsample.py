@@ -1,0 +1,79 @@
+"""K34 measurements: `tca_voxel_downsample` on clouds of the synthetic sweep.
+
+    python tools/bench_voxel_downsample.py --clouds 32 --reps 20        # device events per leaf and variant, the checks
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_voxel_downsample.py --reps 20 --leaves 0.2 --variants default
+
+Every variant's rows are compared with the first variant's on all clouds, and those with the definition on the first
+cloud.  The figure of a variant is its whole launch (five kernels), the median of `--reps` event-timed launches.
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+VARIANTS = {"default": {}, "wave_on": {"wave": True}, "wave_off": {"wave": False}, "lds_on": {"lds": True},
+            "lds_off": {"lds": False}, "saved_on": {"saved": True}, "saved_off": {"saved": False},
+            "all_off": {"wave": False, "lds": False, "saved": False}}
+
+
+def timed(fn, reps):
+    """Sorted microseconds of `reps` event-timed calls of `fn`, after three warm-ups."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in ev:
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    return sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clouds", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--leaves", default="0.1,0.2,0.5")
+    ap.add_argument("--variants", default=",".join(VARIANTS), help="comma-separated, of " + ", ".join(VARIANTS))
+    ap.add_argument("--no-host", action="store_true", help="skip timing the host definition")
+    a = ap.parse_args()
+    from triton_client_amd.ops import voxel_downsample as V
+    from triton_client_amd.ops.cloud_common import CloudLayout
+    from triton_client_amd.utils.synthetic import LidarSpec, lidar_sweep
+
+    spec = LidarSpec(sensor_height=3.23)
+    clouds = [np.frombuffer(lidar_sweep(spec, s).tobytes(), np.float32).reshape(-1, 4).copy() for s in range(a.clouds)]
+    lay = CloudLayout(16, (0, 4, 8, 12), (7, 7, 7, 7))
+    op = V.VoxelDownsampler("cuda")
+    out = {"clouds": a.clouds, "points_per_cloud": len(clouds[0]), "defaults": V.DEFAULTS}
+    for leaf in (float(t) for t in a.leaves.split(",")):
+        o = V.VoxelOptions(leaf=leaf)
+        call = op.prepare([c.tobytes() for c in clouds], [len(c) for c in clouds], lay, o)
+        times, rows = {}, {}
+        for name in a.variants.split(","):
+            times[name] = timed(lambda: V.launch(call, **VARIANTS[name]), a.reps)
+            rows[name] = V.rows_of(call.out[:call.out_bytes].cpu().numpy(), call)
+        first = next(iter(rows))
+        assert all(x.tobytes() == y.tobytes() for r in rows.values() for x, y in zip(r, rows[first])), "the variants differ"
+        t0 = time.perf_counter()
+        want = V.downsample_numpy(clouds[0], o)
+        host = None if a.no_host else round((time.perf_counter() - t0) * 1e3 * a.clouds, 1)
+        assert rows[first][0].tobytes() == want.tobytes(), "not the definition's bytes"
+        out[f"leaf_{leaf:g}"] = {"voxels_per_cloud": round(float(np.mean([len(r) for r in rows[first]]))),
+                                 "table_bytes": call.table_bytes, "d2h_bytes": 16 * sum(len(r) for r in rows[first]),
+                                 **{f"{k}_us": {"median": round(v[len(v) // 2], 1), "min": round(v[0], 1),
+                                                "max": round(v[-1], 1)} for k, v in times.items()},
+                                 "numpy_ms_all_clouds_from_cloud0": host}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

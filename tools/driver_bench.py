@@ -138,6 +138,9 @@ def main():
     ap.add_argument("--grid", action="store_true",
                     help="LiDAR side: also publish every cloud as a ray-cast OccupancyGrid, the sensor height the synthetic "
                          "sweep's and the other options at their defaults (RosInference3D grid_topic)")
+    ap.add_argument("--voxel", action="store_true",
+                    help="LiDAR side: also publish every cloud thinned on a voxel grid, the options at their defaults "
+                         "(RosInference3D voxel_topic)")
     ap.add_argument("--clusters-plain", action="store_true",
                     help="--clusters: one set of atomics per point instead of one per run of a wave (aggregate = 0)")
     ap.add_argument("--clusters-oriented", action="store_true",
@@ -276,7 +279,8 @@ def main():
                              **({"clusters_topic": "/pc_clusters", "cluster_fit": {} if a.clusters_oriented else None,
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.clusters else {}),
                              **({"grid_topic": "/pc_grid",
-                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.grid else {}))
+                                 "ground_options": {"sensor_height": spec.sensor_height}} if a.grid else {}),
+                             **({"voxel_topic": "/pc_voxels"} if a.voxel else {}))
         if a.clusters:
             from triton_client_amd.inference.engines import Detector3D
             extractor = Detector3D.cluster_extractor(eng3)
@@ -305,6 +309,8 @@ def main():
         osub = compat.Subscriber("/pc_grid", msgs.OccupancyGrid,
                                  lambda m: grids.append(np.bincount(m.data.view(np.uint8), minlength=256)[[100, 0, 255]]),
                                  bus=bus) if a.grid else None
+        thinned = []
+        vsub = compat.Subscriber("/pc_voxels", msgs.PointCloud2, lambda m: thinned.append(m.width), bus=bus) if a.voxel else None
         drv.start_inference(spin=False)
         _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[:warm], window, a.timeout,
              side=("/cam_det", dets[:warm]) if dets else None)
@@ -314,6 +320,7 @@ def main():
         del scans[:]
         del boxes[:]
         del grids[:]
+        del thinned[:]
         for v in split.values():
             del v[:]
         n, dt, ok = _run(bus, "/pc", "/pc_out", msgs.BoundingBoxArray, msgs_in[warm:], window, a.timeout,
@@ -331,6 +338,8 @@ def main():
             csub.unregister()
         if osub is not None:
             osub.unregister()
+        if vsub is not None:
+            vsub.unregister()
         if info is not None:
             eng3.close()
         out["lidar"] = {"messages": n, "complete": ok, "seconds": round(dt, 3), "msgs_per_s": round(n / dt, 1),
@@ -403,6 +412,14 @@ def main():
             mean = (np.sum(grids, 0) / max(1, len(grids))).round().astype(int).tolist() if grids else [0, 0, 0]
             out["lidar"]["grid"] = {"messages": len(grids), "occupied_cells": mean[0], "free_cells": mean[1],
                                     "unknown_cells": mean[2]}
+        if a.voxel:
+            from triton_client_amd.inference.engines import Detector3D
+            from triton_client_amd.ops.voxel_downsample import device_enabled
+            kind = "tca_voxel_downsample" if Detector3D.voxel_downsampler(eng3).gpu and device_enabled() else "host definition"
+            print(f"voxel downsample: {kind}", file=sys.stderr)
+            out["lidar"]["output"] += f" + voxel cloud leaf {drv.voxel_options.leaf[0]:g} ({kind})"
+            out["lidar"]["voxel_downsampler"] = kind
+            out["lidar"]["voxels"] = {"messages": len(thinned), "points_per_cloud": round(sum(thinned) / max(1, len(thinned)))}
         if a.tracks:
             trk = drv.tracker()
             ts = trk.state()

@@ -112,6 +112,11 @@ _KERNEL_SIGS = {
     # keys), aggregate (1; 0: one atomic per point), stage_keys (0; 1: near / far in LDS in the cell pass), cells, its
     # bytes, keys, its bytes, out, its bytes, stream (csrc/kernels/occupancy_grid.hip)
     "tca_occupancy_grid": [P, L, P, P, P, I, I, I, I, I, I, P, I, F, F, F, I, I, I, F, I, I, I, P, L, P, L, P, L, P],
+    # data, data bytes, frame_off, frame_n, ns (HOST int32 [B]), slots (HOST int32 [B]: every cloud's table size), B,
+    # point_step, off x/y/z/intensity (-1: none), float32 leaf x/y/z, min_points, wave (1; 0: no reduction over a
+    # wave's runs), lds (1: a workgroup table in LDS), saved (1; 0: the scatter probes again), table, its bytes, memo,
+    # its bytes, blocks, its bytes, out, its bytes, counts, stream (csrc/kernels/voxel_downsample.hip)
+    "tca_voxel_downsample": [P, L, P, P, P, P, I, I, I, I, I, I, F, F, F, I, I, I, I, P, L, P, L, P, L, P, L, P, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

@@ -7,9 +7,10 @@ import sys
 
 from .common import (DATA, add_cluster_flags, add_depth_flags, add_framework_flags, add_grid_flags, add_ground_flags,
                      add_range_flags,
-                     add_reference_flags, add_scan_flags, add_track_flags, bev_view, cluster_fit_options, cluster_options,
-                     depth_options, grid_options, ground_options,
-                     labels_arg, load_params, range_options, scan_options, setup_logging, track_options)
+                     add_reference_flags, add_scan_flags, add_track_flags, add_voxel_flags, bev_view, cluster_fit_options,
+                     cluster_options, depth_options, grid_options, ground_options,
+                     labels_arg, load_params, range_options, scan_options, setup_logging, track_options,
+                     voxel_options)
 from .engines import engine_3d, export_if_asked, maybe_data_parallel
 
 
@@ -48,6 +49,9 @@ def parse_args(argv=None):
     add_grid_flags(p, "write every cloud as a ray-cast nav_msgs/OccupancyGrid (100 where obstacle returns fell, 0 where a return "
                       "proves the cell free, -1 elsewhere; the --ground-* flags say how the cloud is split) to the output "
                       "bag on this topic")
+    add_voxel_flags(p, "write every cloud thinned on a voxel grid (a PointCloud2 of x, y, z, intensity, one centroid per "
+                       "occupied voxel in the order of the voxels' first points; pcl_ros VoxelGrid) to the output bag on "
+                       "this topic")
     flags = p.parse_args(argv)
     flags.calibration, flags.range_options = range_options(flags, p.error)  # a usage error ends here
     flags.calibration, flags.depth_options = depth_options(flags, p.error)
@@ -56,6 +60,7 @@ def parse_args(argv=None):
     flags.cluster_options = cluster_options(flags, p.error)
     flags.cluster_fit = cluster_fit_options(flags, p.error)
     flags.grid_options = grid_options(flags, p.error)
+    flags.voxel_options = voxel_options(flags, p.error)
     return flags
 
 
@@ -92,7 +97,8 @@ def main(argv=None) -> int:
                          ground_options=flags.ground_options, clusters_topic=flags.clusters_topic or None,
                          cluster_options=flags.cluster_options, cluster_fit=flags.cluster_fit,
                          grid_topic=flags.grid_topic or None, grid_options=flags.grid_options,
-                         grid_frame_id=flags.grid_frame_id or "")
+                         grid_frame_id=flags.grid_frame_id or "", voxel_topic=flags.voxel_topic or None,
+                         voxel_options=flags.voxel_options)
     n = drv.start_inference()
     export_if_asked(flags, engine)
     if info is not None:

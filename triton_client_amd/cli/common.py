@@ -634,6 +634,49 @@ def grid_options(flags, error=None):
         fail(f"{flag_of.get(str(e).split()[0], '--grid-topic')}: {e}")
 
 
+def add_voxel_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
+    """--voxel-topic and --voxel-* (``ops/voxel_downsample.py``).  The option flags default to None
+    so that one given without the topic is seen."""
+    p.add_argument("--voxel-topic", default="", metavar="TOPIC", help=topic_help)
+    p.add_argument("--voxel-leaf", default=None, metavar="L|LX,LY,LZ",
+                   help="side of a voxel in metres, one number or one per axis (default 0.2; 0.01..100)")
+    p.add_argument("--voxel-min-points", type=int, default=None, metavar="N",
+                   help="a voxel is kept from this many points (default 1; PCL's min_points_per_voxel)")
+
+
+def voxel_options(flags, error=None):
+    """The ``VoxelOptions`` of the --voxel-* flags, None without --voxel-topic.  A --voxel-* flag
+    without the topic, a leaf that is no ``L`` or ``LX,LY,LZ`` and an option out of range are usage
+    errors that name the flag, reported like :func:`grid_options`'s."""
+    def fail(msg):
+        if error is not None:
+            error(msg)
+        raise ValueError(msg)
+
+    if not flags.voxel_topic:
+        for attr in ("voxel_leaf", "voxel_min_points"):
+            if getattr(flags, attr) is not None:
+                fail(f"--{attr.replace('_', '-')} needs --voxel-topic TOPIC")
+        return None
+    from ..ops.voxel_downsample import VoxelOptions
+
+    kw = {}
+    if flags.voxel_leaf is not None:
+        try:
+            sides = tuple(float(t) for t in flags.voxel_leaf.split(","))
+        except ValueError:
+            sides = ()
+        if len(sides) not in (1, 3):
+            fail(f"--voxel-leaf: want L or LX,LY,LZ, e.g. 0.2, got {flags.voxel_leaf!r}")
+        kw["leaf"] = sides[0] if len(sides) == 1 else sides
+    if flags.voxel_min_points is not None:
+        kw["min_points"] = flags.voxel_min_points
+    try:
+        return VoxelOptions(**kw)
+    except ValueError as e:
+        fail(f"{ {'leaf': '--voxel-leaf', 'min_points': '--voxel-min-points'}.get(str(e).split()[0], '--voxel-topic')}: {e}")
+
+
 def bev_view(engine, res: float, enabled):
     """The ``BevView`` of the --bev-* flags: the engine's point-cloud range (the KITTI
     range for an engine that does not know its model's) at ``res`` metres per pixel; None

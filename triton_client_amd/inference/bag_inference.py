@@ -22,7 +22,7 @@ from typing import Optional
 
 from ..ros.bag import Bag
 from .ros_inference import RosInference
-from .ros_inference3d import EVERY_OUTPUT, RosInference3D
+from .ros_inference3d import EVERY_MESSAGE, RosInference3D
 
 
 def _ingest(engine):
@@ -138,7 +138,8 @@ class BagInference3D(RosInference3D):
         ``NNNN.png`` (``16UC1`` only; the topic defaults to ``<pub_topic>/depth``).  With
         ``scan_topic`` every cloud's ``LaserScan`` is written on that topic, with ``obstacles_topic``
         / ``ground_topic`` its obstacle and ground clouds, with ``clusters_topic`` the boxes of its
-        obstacle clusters (oriented with ``cluster_fit``), with ``grid_topic`` its ``OccupancyGrid``."""
+        obstacle clusters (oriented with ``cluster_fit``), with ``grid_topic`` its ``OccupancyGrid``, with ``voxel_topic``
+        the cloud thinned on a voxel grid."""
         if depth_out and not kw.get("depth_topic"):
             kw["depth_topic"] = ((kw.get("params") or {}).get("pub_topic") or "") + "/depth"
         super().__init__(channel, client, **kw)
@@ -188,7 +189,7 @@ class BagInference3D(RosInference3D):
                     if ob is not None:
                         ob.write(p["sub_topic"], m)
                         ob.write(p["pub_topic"], r.boxes)
-                        for name, _ in EVERY_OUTPUT:
+                        for name, _ in EVERY_MESSAGE:
                             if getattr(r, name) is not None:
                                 ob.write(self.side_topic(name), getattr(r, name))
                     if self.depth_out:

@@ -310,6 +310,19 @@ class Detector3D(ABC):
         cloud's stamp, in frame ``frame_id`` (the cloud's when empty)."""
         return Detector3D.grid_mapper(self).messages(clouds, opts, ground, frame_id)  # (duck-typed too)
 
+    def voxel_downsampler(self):
+        """This engine's :class:`~triton_client_amd.ops.voxel_downsample.VoxelDownsampler`, made once
+        like :meth:`laser_scanner` (``tca_voxel_downsample`` on the engine's GPU, else the host definition)."""
+        from ..ops.voxel_downsample import VoxelDownsampler
+
+        return Detector3D._made_once(self, "_voxel_downsampler", VoxelDownsampler)
+
+    def downsample_clouds(self, clouds: Sequence[msgs.PointCloud2], opts) -> List[msgs.PointCloud2]:
+        """Each cloud thinned on a voxel grid: per cloud one ``PointCloud2`` of x, y, z, intensity with
+        the cloud's header, one centroid per voxel in the order of the voxels' first points (``opts``: a
+        :class:`~triton_client_amd.ops.voxel_downsample.VoxelOptions`)."""
+        return Detector3D.voxel_downsampler(self).messages(clouds, opts)  # (duck-typed too)
+
     def label_points(self, clouds: Sequence[msgs.PointCloud2], preds: Sequence[dict],
                      idx_per_cloud: Optional[Sequence] = None) -> List[tuple]:
         """Which detection owns which point: per cloud ``(owner [N] int32, count [K] int32,

@@ -78,9 +78,17 @@ the prediction as ``pred["clusters"]``; every other message keeps its bytes.  Wi
 (``ops/occupancy_grid.py``: ``tca_occupancy_grid`` on an engine's GPU, behind its own
 ``tca_ground_split`` launch): 100 where obstacle returns fell, 0 where a return proves the cell
 free, -1 elsewhere, with the cloud's stamp and seq, in frame ``grid_frame_id`` (the cloud's when
-empty).  It is published last of the cloud's messages (:data:`MAP_OUTPUTS`;
-:data:`EVERY_OUTPUT` is what the publishers loop over) and rides in the prediction as
+empty).  It is published last of the cloud's messages but the thinned cloud below
+(:data:`MAP_OUTPUTS`, the end of :data:`EVERY_OUTPUT`) and rides in the prediction as
 ``pred["grid"]``; every other message keeps its bytes.
+
+``voxel_topic`` (with ``voxel_options``, a ``VoxelOptions`` or a dict of its fields): the driver
+also publishes, per cloud and with the cloud's header, the cloud thinned on a voxel grid, a
+``PointCloud2`` of x, y, z, intensity with one centroid per occupied voxel
+(``ops/voxel_downsample.py``: ``tca_voxel_downsample`` on an engine's GPU).  It is published last
+of the cloud's messages (:data:`FILTERED_OUTPUTS`; :data:`EVERY_MESSAGE` is what the publishers
+loop over) and rides in the prediction as ``pred["voxels"]``; every other message keeps its bytes.
+The data-parallel ring engines refuse the option.
 
 Whatever is on, one cloud makes one :class:`CloudResult`: the box message, the prediction and
 one field per option above, None where the option is off (or, for ``ranged``, where the cloud
@@ -164,7 +172,7 @@ def boxes_to_detection3d(pred: dict, idx, header: msgs.Header, ids=None) -> msgs
 
 @dataclasses.dataclass
 class CloudResult:
-    """What the driver made of one cloud.  ``ranged``, ``depth``, ``grid``, ``clusters``, ``scan``,
+    """What the driver made of one cloud.  ``ranged``, ``depth``, ``grid``, ``voxels``, ``clusters``, ``scan``,
     ``obstacles`` and ``ground`` are the objects that also ride in ``pred`` under those keys."""
     boxes: object  # BoundingBoxArray, or Detection3DArray
     pred: dict
@@ -174,6 +182,7 @@ class CloudResult:
     ranged: Optional[msgs.Detection2DArray] = None
     depth: Optional[msgs.Image] = None
     grid: Optional[msgs.OccupancyGrid] = None
+    voxels: Optional[msgs.PointCloud2] = None
     clusters: object = None  # a message of the box message's type
     scan: Optional[msgs.LaserScan] = None
     obstacles: Optional[msgs.PointCloud2] = None
@@ -195,7 +204,10 @@ OBJECT_OUTPUTS = (("clusters", None),)
 PUBLISHED = ALL_OUTPUTS + OBJECT_OUTPUTS
 # The maps a planner reads: published last of all.
 MAP_OUTPUTS = (("grid", msgs.OccupancyGrid),)
-EVERY_OUTPUT = PUBLISHED + MAP_OUTPUTS  # what the publishers, ``_publish`` and the bag writer loop over
+EVERY_OUTPUT = PUBLISHED + MAP_OUTPUTS
+# The cloud itself, filtered: published after the maps.
+FILTERED_OUTPUTS = (("voxels", msgs.PointCloud2),)
+EVERY_MESSAGE = EVERY_OUTPUT + FILTERED_OUTPUTS  # what the publishers, ``_publish`` and the bag writer loop over
 
 
 class RosInference3D(BaseInference):
@@ -211,7 +223,7 @@ class RosInference3D(BaseInference):
                  scan_options=None, scan_frame_id: str = "", obstacles_topic: Optional[str] = None,
                  ground_topic: Optional[str] = None, ground_options=None, clusters_topic: Optional[str] = None,
                  cluster_options=None, cluster_fit=None, grid_topic: Optional[str] = None, grid_options=None,
-                 grid_frame_id: str = ""):
+                 grid_frame_id: str = "", voxel_topic: Optional[str] = None, voxel_options=None):
         super().__init__(channel, client)
         self._params = params or {}
         self.engine = engine or RemoteDetector3D(channel, client, z_offset=z_offset, mode=mode, wire=wire)
@@ -268,6 +280,15 @@ class RosInference3D(BaseInference):
 
             if not isinstance(grid_options, GridOptions):
                 self.grid_options = GridOptions(**(grid_options or {}))  # a bad option fails here
+        self.voxel_topic, self.voxel_options = voxel_topic or None, voxel_options
+        if self.voxel_topic:
+            from ..ops.voxel_downsample import VoxelOptions
+
+            if not getattr(self.engine, "voxel_out", True):
+                raise ValueError(f"{type(self.engine).__name__} does not downsample clouds: the data-parallel ring "
+                                 "engines keep no cloud on rank 0's device; run without --voxel-topic")
+            if not isinstance(voxel_options, VoxelOptions):
+                self.voxel_options = VoxelOptions(**(voxel_options or {}))  # a bad option fails here
         self.cluster_fit = None
         if cluster_fit is not None:
             from ..ops.cluster_fit import as_options
@@ -279,7 +300,7 @@ class RosInference3D(BaseInference):
         self.queue_size, self.metrics = queue_size, metrics
         self.frames = 0
         self.sub = self.pub = None
-        self.side_pubs = {}  # the publishers of the side outputs that are on, by EVERY_OUTPUT name
+        self.side_pubs = {}  # the publishers of the side outputs that are on, by EVERY_MESSAGE name
         # batch > 1: the reference's queue of 50 becomes a latest-wins window
         # drained as micro-batches (one engine call per batch), re-published in
         # header.seq order (see .batching)
@@ -291,7 +312,7 @@ class RosInference3D(BaseInference):
         t = msgs.BoundingBoxArray if self.jsk else msgs.Detection3DArray
         self.pub = compat.Publisher(p["pub_topic"], t, queue_size=1, bus=self.bus)
         self.side_pubs = {name: compat.Publisher(self.side_topic(name), mtype or t, queue_size=1, bus=self.bus)
-                          for name, mtype in EVERY_OUTPUT if self.side_topic(name)}
+                          for name, mtype in EVERY_MESSAGE if self.side_topic(name)}
         if self.ranged_topic:
             self.camera_sub = compat.Subscriber(self.camera_detections_topic, msgs.Detection2DArray,
                                                 self.pairer.push, queue_size=None, bus=self.bus)
@@ -328,8 +349,13 @@ class RosInference3D(BaseInference):
         self.bev_topic = topic
         self.bev_view = view or (BevView.for_model(cfg) if getattr(cfg, "voxel", None) is not None else BevView())
 
+    @property
+    def voxels_topic(self) -> Optional[str]:
+        """``voxel_topic`` under the name of its ``CloudResult`` field, which :meth:`side_topic` asks for."""
+        return self.voxel_topic
+
     def side_topic(self, name: str) -> Optional[str]:
-        """The topic of the side output ``name`` of :data:`EVERY_OUTPUT`, None when it is off."""
+        """The topic of the side output ``name`` of :data:`EVERY_MESSAGE`, None when it is off."""
         return getattr(self, name + "_topic")
 
     def _engine(self, name: str, *args, **kw):
@@ -340,9 +366,9 @@ class RosInference3D(BaseInference):
 
     def _publish(self, r: CloudResult) -> None:
         """One cloud's messages: the box message, then every side output it has, in
-        :data:`EVERY_OUTPUT` order."""
+        :data:`EVERY_MESSAGE` order."""
         self.pub.publish(r.boxes)
-        for name, _ in EVERY_OUTPUT:
+        for name, _ in EVERY_MESSAGE:
             m = getattr(r, name)
             if m is not None:
                 self.side_pubs[name].publish(m)
@@ -398,6 +424,9 @@ class RosInference3D(BaseInference):
         if self.grid_topic:
             with timer("occupancy_grid"):
                 self._grid(clouds, out)
+        if self.voxel_topic:
+            with timer("voxel_downsample"):
+                self._voxels(clouds, out)
         self.frames += len(clouds)
         if self.metrics is not None:
             self.metrics.stage("frame3d", (time.perf_counter() - t0) / max(len(clouds), 1))
@@ -460,6 +489,12 @@ class RosInference3D(BaseInference):
         res = self._engine("occupancy_grids", clouds, self.grid_options, self.ground_options, self.grid_frame_id)
         for r, m in zip(out, res):
             r.grid = r.pred["grid"] = m
+
+    def _voxels(self, clouds, out: List[CloudResult]) -> None:
+        """``voxels`` and ``pred["voxels"]`` of every result: the cloud thinned on a voxel grid.  One
+        call per batch."""
+        for r, m in zip(out, self._engine("downsample_clouds", clouds, self.voxel_options)):
+            r.voxels = r.pred["voxels"] = m
 
     def tracker(self):
         """The engine's tracker, made with ``track_options`` on first use."""

@@ -3,7 +3,8 @@ labeler (``ops/points_in_boxes.py``, K22), the bird's-eye-view painter (``ops/be
 the camera ranger (``ops/range2d.py``, K26), the depth imager (``ops/depth_image.py``, K27), the
 laser scanner (``ops/laser_scan.py``, K29), the ground splitter (``ops/ground.py``, K30), the cluster
 extractor (``ops/cluster.py``, K31) and the grid mapper (``ops/occupancy_grid.py``, K33, which like the cluster
-extractor stages through a ground splitter of its own): where
+extractor stages through a ground splitter of its own) and the voxel downsampler
+(``ops/voxel_downsample.py``, K34): where
 a cloud's fields lie (:class:`CloudLayout`), which of them a kernel can read in place
 (:func:`fields_f32`), the byte layout of one staged batch (:func:`plan_staging`,
 :func:`fill_staging`: no torch in either), and the device side of such an op

@@ -1,0 +1,408 @@
+"""K34 — the cloud thinned on a voxel grid: one centroid per occupied voxel.
+
+Registration, mapping, recording and visualisation all start from a downsampled cloud; ROS users
+run ``pcl_ros``'s ``VoxelGrid`` nodelet for it, a sort or a hash of every point on a CPU core in
+front of the rest of the chain.  Here the driver publishes it per cloud: a ``PointCloud2`` of x, y,
+z, intensity, one record per voxel.  :func:`downsample_numpy` is the definition, bit for bit (the
+pattern of ``ops/occupancy_grid.py``); the HIP kernels of ``tca_voxel_downsample``
+(``csrc/kernels/voxel_downsample.hip``) compute the same bytes from the raw payload with a hash
+table on the device, and :func:`downsample_ref` is a float64 brute force that also names the voxels
+float32 may legitimately fill differently (``docs/precision.md``).
+
+All float arithmetic is float32, every operation rounded on its own (no FMA), IEEE division.
+
+**Valid points.**  A point is valid iff x, y and z are finite and ``|v| <= 512`` (``cluster.LIMIT``);
+every other point belongs to no voxel.  A cloud of more than 2^24 points is a ``ValueError``.
+
+**Voxel index.**  Per axis ``floor(v / f32(leaf))`` as an integer — ``floor``, not truncation:
+-0.05 and +0.05 lie in different voxels.  Its magnitude stays below 2^20 (512 / 0.01), so a voxel
+has the 64-bit key ``(iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20)``.
+
+**Sums.**  Integers, so nothing depends on the order of the points: per coordinate
+``q = int(rint(v * 65536))`` (the product is exact, ``|q| <= 2^25``) and for the intensity
+``qi = int(rint(clamp(i, -65536, 65536) * 4096))``, 0 for a NaN intensity or a cloud without an
+intensity field, each summed in int64.  With at most 2^24 points every sum stays below 2^53.
+
+**A kept voxel** has ``n >= min_points`` points (PCL's ``min_points_per_voxel``).  Its centroid
+coordinate is ``float32(float64(S) / float64(n * 65536))``: one correctly rounded float64 division,
+then one rounding to float32; its intensity the same with 4096.
+
+**Order.**  The kept voxels appear in the order of their first point in the cloud (ascending
+smallest point index), not sorted by key: the sensor's scan order survives, and the device compacts
+without a sort.
+
+Two departures from PCL's ``VoxelGrid``: PCL sums in float in input order and sorts the output by
+voxel index (here: integer sums, first-point order), and every other field (ring, time) is dropped.
+
+Not here: averaging or carrying the other fields, ``filter_field_name`` limits and ``leaf_layout``,
+feeding the thinned cloud into the detectors or the other side outputs, tf.
+"""
+from __future__ import annotations
+
+import math
+import os
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .. import _native
+from ..ros import msgs
+from . import cluster as C
+from .cloud_common import CloudLayout, CloudStager, _align, cloud_bytes, cloud_xyzi, fields_f32, plan_staging
+from .laser_scan import _number
+from .range2d import INT31
+
+MAX_FRAMES = 64  # clouds per launch
+MAX_POINTS = 2 ** 24  # of one cloud
+MAX_TABLE = 2 ** 30  # bytes of one launch's hash tables
+LEAF_MIN, LEAF_MAX = 0.01, 100.0
+BIAS = 2 ** 20  # added to a voxel index in the key
+QC, QI = 65536, 4096  # units per metre of the coordinate sums, per unit of the intensity sums
+I_LIMIT = 65536.0  # an intensity is clamped to this in magnitude
+SLOT = 48  # bytes of a table slot: key, four int64 sums, count, first point
+BLOCK = 256  # points per block of the device's counts
+RECORD = 16  # bytes of an output record
+# The launch's variants as they are run (``profiles/voxel_downsample/README.md`` has the measurements).
+DEFAULTS = {"wave": True, "lds": True, "saved": True}
+
+
+def device_enabled() -> bool:
+    """``TCA_DEVICE_VOXEL=0`` keeps the definition on GPU engines too."""
+    return os.environ.get("TCA_DEVICE_VOXEL", "1") != "0"
+
+
+# ----------------------------------------------------------------------------- options
+@dataclass(frozen=True)
+class VoxelOptions:
+    leaf: object = 0.2  # one number, or (lx, ly, lz)
+    min_points: int = 1
+
+    def __post_init__(self):
+        v = self.leaf
+        if isinstance(v, (tuple, list)):
+            if len(v) != 3:
+                raise ValueError(f"leaf must be one number or (lx, ly, lz), got {v!r}")
+            sides = tuple(_number("leaf", s) for s in v)
+        else:
+            sides = (_number("leaf", v),) * 3
+        for s in sides:
+            if not np.float32(LEAF_MIN) <= np.float32(s) <= np.float32(LEAF_MAX):
+                raise ValueError(f"leaf must lie within {LEAF_MIN}..{LEAF_MAX:g} m on every axis, got {v!r}")
+        object.__setattr__(self, "leaf", sides)
+        C._count("min_points", self.min_points, 1, 2 ** 31 - 1)
+
+    @property
+    def l32(self) -> Tuple[np.float32, np.float32, np.float32]:
+        return tuple(np.float32(s) for s in self.leaf)
+
+
+# ------------------------------------------------------------------------- definition
+def _columns(points) -> np.ndarray:
+    p = np.asarray(points, np.float32)
+    p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 3)
+    if len(p) > MAX_POINTS:
+        raise ValueError(f"{len(p)} points in a cloud: at most {MAX_POINTS}")
+    return p
+
+
+def _pack(idx: Sequence[np.ndarray]) -> np.ndarray:
+    ix, iy, iz = (i.astype(np.int64) + BIAS for i in idx)
+    return (iz << 42) | (iy << 21) | ix
+
+
+def keys_numpy(points, opts: VoxelOptions) -> Tuple[np.ndarray, np.ndarray]:
+    """The per-point half of the definition → ``(key [N] int64, valid [N] bool)``; the key is -1
+    where the point is not valid."""
+    p = _columns(points)
+    lim = np.float32(C.LIMIT)
+    with np.errstate(invalid="ignore", over="ignore"):
+        valid = (np.abs(p[:, :3]) <= lim).all(1)  # (a NaN compares false; an infinity is too large)
+        idx = [np.floor((np.where(valid, p[:, j], np.float32(0)) / l).astype(np.float32)) for j, l in enumerate(opts.l32)]
+    return np.where(valid, _pack(idx), -1), valid
+
+
+def quantised(points) -> np.ndarray:
+    """``int64 [N, 4]``: the integers a point adds to its voxel's sums (an invalid point's are not read)."""
+    p = _columns(points)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.zeros((len(p), 4), np.int64)
+        ok = np.abs(p[:, :3]) <= np.float32(C.LIMIT)
+        q[:, :3] = np.rint(np.where(ok, p[:, :3], np.float32(0)) * np.float32(QC))
+        if p.shape[1] >= 4:
+            i = np.where(np.isnan(p[:, 3]), np.float32(0), np.clip(p[:, 3], np.float32(-I_LIMIT), np.float32(I_LIMIT)))
+            q[:, 3] = np.rint(i.astype(np.float32) * np.float32(QI))
+    return q
+
+
+def _voxels(key: np.ndarray, valid: np.ndarray):
+    """→ ``(keys [V], first [V], count [V], order, starts)`` of the distinct valid keys; ``order``
+    sorts the valid points by voxel, ``starts`` is where each voxel's run begins in it."""
+    at = np.nonzero(valid)[0]
+    uniq, inv, count = np.unique(key[at], return_inverse=True, return_counts=True)
+    order = np.argsort(inv, kind="stable")
+    starts = np.cumsum(count) - count
+    return uniq, at[order][starts] if len(uniq) else at[:0], count, at[order], starts
+
+
+def downsample_numpy(points, opts: VoxelOptions) -> np.ndarray:
+    """The definition → ``float32 [K, 4]`` (x, y, z, intensity), one row per kept voxel in the order
+    of its first point.  ``points``: [N, >=3 or 4] float32."""
+    key, valid = keys_numpy(points, opts)
+    uniq, first, count, order, starts = _voxels(key, valid)
+    if not len(uniq):
+        return np.zeros((0, 4), np.float32)
+    sums = np.add.reduceat(quantised(points)[order], starts, axis=0)  # int64: exact
+    keep = np.nonzero(count >= opts.min_points)[0]
+    keep = keep[np.argsort(first[keep], kind="stable")]
+    den = count[keep, None] * np.array([QC, QC, QC, QI], np.int64)
+    return (sums[keep].astype(np.float64) / den.astype(np.float64)).astype(np.float32)
+
+
+def keys_ref(points, opts: VoxelOptions) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Float64, point by point and with nothing of the definition's code → ``(key [N] int64, valid
+    [N] bool, odd [N] bool)``: the index is ``floor(float64(v) / float64(f32(leaf)))``; ``odd`` marks
+    the valid points whose ``d`` lies within ``cluster.CELL_BAND`` (relative, at least of 1) of an
+    integer on any axis."""
+    p = np.asarray(points, np.float32)
+    rows = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 3)[:, :3].astype(np.float64).tolist()
+    leaf = [float(l) for l in opts.l32]
+    key, valid, odd = np.full(len(rows), -1, np.int64), np.zeros(len(rows), bool), np.zeros(len(rows), bool)
+    for n, xyz in enumerate(rows):
+        if not all(abs(v) <= C.LIMIT for v in xyz):  # (a NaN compares false; an infinity is too large)
+            continue
+        d = [v / l for v, l in zip(xyz, leaf)]
+        ix, iy, iz = (math.floor(t) + BIAS for t in d)
+        key[n], valid[n] = iz * 2 ** 42 + iy * 2 ** 21 + ix, True
+        odd[n] = any(abs(t - round(t)) <= C.CELL_BAND * max(abs(t), 1.0) for t in d)
+    return key, valid, odd
+
+
+def downsample_ref(points, opts: VoxelOptions):
+    """Float64 brute force → ``(centroids float64 [K, 4], keys int64 [K], band int64 [...])``: a
+    loop over the points that gathers each voxel's values in a dict (which keeps first-point order)
+    and takes plain float64 means of the voxels of ``min_points`` points or more, with the voxels'
+    keys.  ``band`` holds the keys of the voxels float32 may legitimately fill differently: every
+    voxel that holds, or in float32 holds, an ``odd`` point of :func:`keys_ref`.  ``float32(leaf)``
+    is an input of both evaluations."""
+    p = np.asarray(points, np.float32)
+    p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 3)
+    key, valid, odd = keys_ref(p, opts)
+    band = np.unique(np.concatenate([key[odd], keys_numpy(p, opts)[0][odd]]))
+    members = {}
+    for n, row in enumerate(p.astype(np.float64).tolist()):
+        if valid[n]:
+            i = row[3] if len(row) >= 4 and not math.isnan(row[3]) else 0.0
+            members.setdefault(int(key[n]), []).append(row[:3] + [min(max(i, -I_LIMIT), I_LIMIT)])
+    kept = [(k, m) for k, m in members.items() if len(m) >= opts.min_points]
+    mean = [[math.fsum(r[j] for r in m) / len(m) for j in range(4)] for _, m in kept]
+    return np.array(mean, np.float64).reshape(-1, 4), np.array([k for k, _ in kept], np.int64), band
+
+
+# ---------------------------------------------------------------------------- messages
+def downsample_message(cloud, rows: np.ndarray) -> msgs.PointCloud2:
+    """The rows as an unorganised, dense, little-endian ``PointCloud2`` of 16-byte records with the
+    cloud's header: FLOAT32 x, y, z at 0, 4, 8 and, when the input cloud has one, ``intensity`` at
+    12 (the dword is there either way)."""
+    a = np.ascontiguousarray(rows, "<f4").reshape(-1, 4)
+    fields = [msgs.PointField("x", 0, 7, 1), msgs.PointField("y", 4, 7, 1), msgs.PointField("z", 8, 7, 1)]
+    if any(f.name == "intensity" for f in cloud.fields):
+        fields.append(msgs.PointField("intensity", 12, 7, 1))
+    return msgs.PointCloud2(header=cloud.header, height=1, width=len(a), fields=fields, is_bigendian=False,
+                            point_step=RECORD, row_step=RECORD * len(a), data=a.tobytes(), is_dense=True)
+
+
+def downsample_cloud_numpy(cloud, opts: VoxelOptions, lay: Optional[CloudLayout] = None) -> np.ndarray:
+    """One cloud through the definition → its rows."""
+    return downsample_numpy(cloud_xyzi(cloud, lay), opts)
+
+
+# --------------------------------------------------------------------------------- GPU
+def slots_for(n: int) -> int:
+    """The default table size of a cloud of ``n`` points: the power of two at or above ``2 n``."""
+    return max(2, 1 << (2 * int(n) - 1).bit_length()) if n > 0 else 2
+
+
+def most_clouds(n: int) -> int:
+    """How many clouds of ``n`` points fit one launch: 64, and :data:`MAX_TABLE` bytes of tables."""
+    return max(1, min(MAX_FRAMES, MAX_TABLE // (SLOT * slots_for(n))))
+
+
+def parts(idx, clouds):
+    """The cut of a layout's clouds into launches of less than 2^31 staged bytes and of at most
+    :func:`most_clouds` of the largest cloud among them: 64 clouds, and :data:`MAX_TABLE` bytes of
+    default-sized tables (a single cloud is never refused here)."""
+    part, size, big = [], 0, 0
+    for i in idx:
+        nb = _align(len(clouds[i].data)) + 16
+        n = int(clouds[i].width) * int(clouds[i].height)
+        if part and (len(part) >= most_clouds(max(big, n)) or size + nb >= INT31):
+            yield part
+            part, size, big = [], 0, 0
+        part.append(i)
+        size += nb
+        big = max(big, n)
+    if part:
+        yield part
+
+
+@dataclass
+class VoxelCall:
+    """One prepared launch: device views of its inputs, workspace and output."""
+    data: torch.Tensor
+    data_bytes: int
+    frame_off: torch.Tensor
+    frame_n: torch.Tensor
+    table: torch.Tensor  # uint8 view of the clouds' tables, one after the other, 48 bytes a slot
+    memo: torch.Tensor  # uint8 view of int32, one per staged point: its slot when it writes its voxel's record, else -1
+    blocks: torch.Tensor  # uint8 view of int32 [B][nblk + 1]: per block its writers, then its offset
+    out: torch.Tensor  # uint8: cloud b's records from 16 * (points before it), then counts int32 [B]
+    layout: CloudLayout
+    batch: int
+    ns: Tuple[int, ...]
+    slots: Tuple[int, ...]
+    opts: VoxelOptions
+
+    @property
+    def table_bytes(self) -> int:
+        return SLOT * sum(self.slots)
+
+    @property
+    def memo_bytes(self) -> int:
+        return 4 * sum(self.ns)
+
+    @property
+    def blocks_bytes(self) -> int:
+        return 4 * self.batch * ((max(self.ns, default=0) + BLOCK - 1) // BLOCK + 1)
+
+    @property
+    def rows_bytes(self) -> int:
+        return RECORD * sum(self.ns)
+
+    @property
+    def out_bytes(self) -> int:
+        return self.rows_bytes + 4 * self.batch
+
+    @property
+    def counts(self) -> torch.Tensor:
+        return self.out[self.rows_bytes:self.out_bytes].view(torch.int32)
+
+
+def launch(c: VoxelCall, stream=None, wave: Optional[bool] = None, lds: Optional[bool] = None,
+           saved: Optional[bool] = None) -> None:
+    """The launch alone (five kernels on ``stream``): no allocation, no copy, no sync.  ``wave``:
+    runs of equal voxels of a wave are reduced with shuffles first; ``lds``: a workgroup gathers its
+    span of points in a table in LDS; ``saved``: the scatter reads the slot the count pass kept
+    instead of probing the table again.  None: :data:`DEFAULTS`."""
+    wave, lds, saved = (DEFAULTS[k] if v is None else v for k, v in (("wave", wave), ("lds", lds), ("saved", saved)))
+    p = _native.ptr
+    o, r = c.layout.offsets, c.opts
+    ns, slots = np.asarray(c.ns, np.int32), np.asarray(c.slots, np.int32)
+    _native.call("tca_voxel_downsample", p(c.data), c.data_bytes, p(c.frame_off), p(c.frame_n), ns.ctypes.data,
+                 slots.ctypes.data, c.batch, c.layout.point_step, o[0], o[1], o[2], o[3], *(float(l) for l in r.l32),
+                 int(r.min_points), 1 if wave else 0, 1 if lds else 0, 1 if saved else 0, p(c.table), c.table_bytes,
+                 p(c.memo), c.memo_bytes, p(c.blocks), c.blocks_bytes, p(c.out), c.rows_bytes, p(c.counts),
+                 _native.stream_ptr(stream))
+
+
+def layout_device_ok(lay: CloudLayout) -> bool:
+    """What ``tca_voxel_downsample`` reads in place: little-endian FLOAT32 x, y, z inside the
+    record, and an intensity that is FLOAT32 too or absent."""
+    return fields_f32(lay, (0, 1, 2, 3) if lay.offsets[3] >= 0 else (0, 1, 2))
+
+
+def rows_of(host: np.ndarray, c: VoxelCall) -> List[np.ndarray]:
+    """Per cloud its rows ``float32 [K, 4]`` (copies) of a launch's output bytes (``out_bytes`` of them)."""
+    counts = host[c.rows_bytes:c.out_bytes].view("<i4")
+    res, at = [], 0
+    for b, n in enumerate(c.ns):
+        k = int(counts[b])
+        res.append(host[RECORD * at:RECORD * (at + k)].view("<f4").reshape(k, 4).copy())
+        at += n
+    return res
+
+
+class VoxelDownsampler(CloudStager):
+    """Thins clouds on a voxel grid: on a GPU with ``tca_voxel_downsample`` (its own workspace,
+    stream and pinned staging: one H2D of the payloads per launch group of same-layout clouds, one
+    launch, the counts back, then only the used part of every cloud's slot), on the CPU — and with
+    ``TCA_DEVICE_VOXEL=0`` — with the definition.  Clouds the kernel does not take (non-FLOAT32 or
+    big-endian x, y, z, an intensity that is present but not FLOAT32) run the definition with one
+    warning.  ``wave``, ``lds``, ``saved``: the launch's variants, None for :data:`DEFAULTS`."""
+
+    wave = lds = saved = None
+
+    def prepare(self, payloads: Sequence, ns: Sequence[int], layout: CloudLayout, opts: VoxelOptions, stream=None,
+                misalign: int = 0, slots: Optional[Sequence[int]] = None) -> VoxelCall:
+        """Stage one batch (``payloads[b]``: the bytes of ``ns[b]`` points of ``layout``) in pinned
+        memory and upload it with one H2D copy on ``stream``.  ``misalign``: start every payload
+        this many bytes past a 16-byte boundary; ``slots``: the table size of every cloud (a power
+        of two at or above its points) in place of :func:`slots_for`."""
+        if not layout_device_ok(layout):
+            raise ValueError(f"tca_voxel_downsample does not take this layout: {layout}")
+        B = len(payloads)
+        ns = [int(n) for n in ns]
+        if not 1 <= B <= MAX_FRAMES:
+            raise ValueError(f"{B} clouds do not fit one call (1..{MAX_FRAMES}): split the batch")
+        if max(ns) > MAX_POINTS:
+            raise ValueError(f"{max(ns)} points in a cloud: at most {MAX_POINTS}")
+        slots = [slots_for(n) for n in ns] if slots is None else [int(s) for s in slots]
+        if len(slots) != B or any(s < max(n, 2) or s & (s - 1) for s, n in zip(slots, ns)):
+            raise ValueError(f"slots must be one power of two per cloud, at or above its points: {slots} for {ns}")
+        data_bytes = plan_staging(ns, layout.point_step, misalign, ()).data_bytes  # (refused before any allocation)
+        if data_bytes >= INT31 or (B > 1 and SLOT * sum(slots) > MAX_TABLE):
+            raise ValueError(f"{data_bytes} payload bytes and {SLOT * sum(slots)} table bytes do not fit one call: "
+                             "split the batch")
+        dev, plan, view = self._stage("voxel_in", payloads, ns, layout.point_step, misalign, [], stream)
+        c = VoxelCall(data=dev, data_bytes=data_bytes, frame_off=view("frame_off", B, torch.int64),
+                      frame_n=view("frame_n", B, torch.int32), table=None, memo=None, blocks=None, out=None,
+                      layout=layout, batch=B, ns=tuple(ns), slots=tuple(slots), opts=opts)
+        c.table = self._device_buf("voxel_table", c.table_bytes)
+        c.memo = self._device_buf("voxel_memo", c.memo_bytes)
+        c.blocks = self._device_buf("voxel_blocks", c.blocks_bytes)
+        c.out = self._device_buf("voxel_out", c.out_bytes)
+        return c
+
+    launch = staticmethod(launch)
+
+    def _fetch_counted(self, c: VoxelCall, st) -> np.ndarray:
+        """The counts, a synchronize, then only the used records of every cloud's slot; the host
+        bytes are laid out like the output."""
+        pin = self._pinned("_pin_out", c.out_bytes)
+        with torch.cuda.stream(st):
+            pin[c.rows_bytes:c.out_bytes].copy_(c.out[c.rows_bytes:c.out_bytes], non_blocking=True)
+        st.synchronize()
+        counts = pin.numpy()[c.rows_bytes:c.out_bytes].view("<i4")
+        with torch.cuda.stream(st):
+            at = 0
+            for b, n in enumerate(c.ns):
+                lo, hi = RECORD * at, RECORD * (at + int(counts[b]))
+                if hi > lo:
+                    pin[lo:hi].copy_(c.out[lo:hi], non_blocking=True)
+                at += n
+        st.synchronize()
+        return pin.numpy()[:c.out_bytes]
+
+    def _run_device(self, payloads, ns, layout, opts):
+        """→ per frame its rows."""
+        with torch.cuda.device(self.device):
+            st = self._own_stream()
+            c = self.prepare(payloads, ns, layout, opts, st)
+            launch(c, st, self.wave, self.lds, self.saved)
+            return rows_of(self._fetch_counted(c, st), c)
+
+    # ---------------------------------------------------------------------- API
+    def downsample(self, clouds: Sequence, opts: VoxelOptions) -> List[np.ndarray]:
+        """Per cloud its rows ``float32 [K, 4]``, in input order."""
+        return self._per_cloud(
+            clouds, lambda i, lay: layout_device_ok(lay),
+            lambda i, lay: downsample_cloud_numpy(clouds[i], opts, lay),
+            lambda lay, part: (*cloud_bytes(clouds, part), lay, opts), self._run_device,
+            lambda i, lay: f"VoxelDownsampler: tca_voxel_downsample takes little-endian FLOAT32 x, y, z and intensity "
+                           f"(got {lay}); such clouds are downsampled on the host",
+            device=self.gpu and device_enabled(), parts=parts)
+
+    def messages(self, clouds: Sequence, opts: VoxelOptions) -> List[msgs.PointCloud2]:
+        """Per cloud its downsampled ``PointCloud2`` message."""
+        return [downsample_message(c, a) for c, a in zip(clouds, self.downsample(clouds, opts))]

@@ -715,6 +715,7 @@ class DataParallelDetector3D(_RingDP):
     ``detect(clouds)`` -> per-cloud {pred_boxes, pred_scores, pred_labels}."""
 
     FIELDS = ("x", "y", "z", "intensity")
+    voxel_out = False  # no cloud stays on rank 0's device: the drivers refuse voxel_topic= for this engine
 
     def __init__(self, local, info: DistInfo, max_out: int = 500, box_dim: int = 7,
                  monitor: Optional[HealthMonitor] = None, nslots: int = 4, comm=None,
