@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--leaves", default="0.1,0.2,0.5")
     ap.add_argument("--variants", default=",".join(VARIANTS), help="comma-separated, of " + ", ".join(VARIANTS))
     ap.add_argument("--no-host", action="store_true", help="skip timing the host definition")
+    ap.add_argument("--normals", type=float, default=0.0, metavar="R",
+                    help="also time tca_voxel_normals alone at this radius, stage on and off, and check its bytes")
     a = ap.parse_args()
     from triton_client_amd.ops import voxel_downsample as V
     from triton_client_amd.ops.cloud_common import CloudLayout
@@ -55,7 +57,7 @@ def main():
     op = V.VoxelDownsampler("cuda")
     out = {"clouds": a.clouds, "points_per_cloud": len(clouds[0]), "defaults": V.DEFAULTS}
     for leaf in (float(t) for t in a.leaves.split(",")):
-        o = V.VoxelOptions(leaf=leaf)
+        o = V.VoxelOptions(leaf=leaf, normal_radius=a.normals)
         call = op.prepare([c.tobytes() for c in clouds], [len(c) for c in clouds], lay, o)
         times, rows = {}, {}
         for name in a.variants.split(","):
@@ -72,6 +74,21 @@ def main():
                                  **{f"{k}_us": {"median": round(v[len(v) // 2], 1), "min": round(v[0], 1),
                                                 "max": round(v[-1], 1)} for k, v in times.items()},
                                  "numpy_ms_all_clouds_from_cloud0": host}
+        if a.normals:  # (the times above are of both entries; these of the second alone, on the records of the last launch)
+            alone, got = {}, {}
+            for stage in (True, False):
+                alone[stage] = timed(lambda: V.launch_normals(call, stage=stage), a.reps)
+                got[stage] = call.normals[:call.rows_bytes].cpu().numpy()
+            rows8 = V.rows_of(call.out[:call.out_bytes].cpu().numpy(), call, got[True])
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(rows8, V.rows_of(call.out[:call.out_bytes].cpu().numpy(), call, got[False]))), "stage on and off differ"
+            t0 = time.perf_counter()
+            want = V.normals_numpy(rows8[0][:, :4], o)
+            assert rows8[0][:, 4:].tobytes() == want.tobytes(), "not the normals' definition's bytes"
+            out[f"leaf_{leaf:g}"]["normals"] = {
+                "radius": a.normals, "numpy_ms_all_clouds_from_cloud0": round((time.perf_counter() - t0) * 1e3 * a.clouds, 1),
+                "no_normal_share": round(float(np.mean([np.isnan(r[:, 4]).mean() for r in rows8 if len(r)])), 4),
+                **{f"stage_{'on' if s else 'off'}_us": {"median": round(v[len(v) // 2], 1), "min": round(v[0], 1),
+                                                         "max": round(v[-1], 1)} for s, v in alone.items()}}
     print(json.dumps(out))
 
 

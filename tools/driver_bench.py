@@ -141,6 +141,9 @@ def main():
     ap.add_argument("--voxel", action="store_true",
                     help="LiDAR side: also publish every cloud thinned on a voxel grid, the options at their defaults "
                          "(RosInference3D voxel_topic)")
+    ap.add_argument("--voxel-normals", type=float, default=0.0, metavar="R",
+                    help="--voxel: with a normal and a curvature per voxel from its neighbours within R metres "
+                         "(VoxelOptions.normal_radius; tca_voxel_normals)")
     ap.add_argument("--clusters-plain", action="store_true",
                     help="--clusters: one set of atomics per point instead of one per run of a wave (aggregate = 0)")
     ap.add_argument("--clusters-oriented", action="store_true",
@@ -280,7 +283,8 @@ def main():
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.clusters else {}),
                              **({"grid_topic": "/pc_grid",
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.grid else {}),
-                             **({"voxel_topic": "/pc_voxels"} if a.voxel else {}))
+                             **({"voxel_topic": "/pc_voxels"} if a.voxel else {}),
+                             **({"voxel_options": {"normal_radius": a.voxel_normals}} if a.voxel and a.voxel_normals else {}))
         if a.clusters:
             from triton_client_amd.inference.engines import Detector3D
             extractor = Detector3D.cluster_extractor(eng3)
@@ -418,6 +422,8 @@ def main():
             kind = "tca_voxel_downsample" if Detector3D.voxel_downsampler(eng3).gpu and device_enabled() else "host definition"
             print(f"voxel downsample: {kind}", file=sys.stderr)
             out["lidar"]["output"] += f" + voxel cloud leaf {drv.voxel_options.leaf[0]:g} ({kind})"
+            if drv.voxel_options.normals:
+                out["lidar"]["output"] += f" with normals r {drv.voxel_options.normal_radius:g}"
             out["lidar"]["voxel_downsampler"] = kind
             out["lidar"]["voxels"] = {"messages": len(thinned), "points_per_cloud": round(sum(thinned) / max(1, len(thinned)))}
         if a.tracks:

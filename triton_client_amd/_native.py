@@ -117,6 +117,10 @@ _KERNEL_SIGS = {
     # wave's runs), lds (1: a workgroup table in LDS), saved (1; 0: the scatter probes again), table, its bytes, memo,
     # its bytes, blocks, its bytes, out, its bytes, counts, stream (csrc/kernels/voxel_downsample.hip)
     "tca_voxel_downsample": [P, L, P, P, P, P, I, I, I, I, I, I, F, F, F, I, I, I, I, P, L, P, L, P, L, P, L, P, P],
+    # tca_voxel_downsample's records, their bytes, its counts, ns and slots (HOST, as it took them), B, the radius in
+    # units of 2^-16 m, stage (0: every lane probes and reads for itself; 1: a cell's candidates go through LDS), the leaf table (now the cell lists'
+    # workspace), its bytes, normals, their bytes, stream (csrc/kernels/voxel_normals.hip)
+    "tca_voxel_normals": [P, L, P, P, P, I, I, I, P, L, P, L, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

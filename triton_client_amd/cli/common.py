@@ -642,6 +642,10 @@ def add_voxel_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
                    help="side of a voxel in metres, one number or one per axis (default 0.2; 0.01..100)")
     p.add_argument("--voxel-min-points", type=int, default=None, metavar="N",
                    help="a voxel is kept from this many points (default 1; PCL's min_points_per_voxel)")
+    p.add_argument("--voxel-normals", type=float, default=None, metavar="R",
+                   help="also estimate a surface normal and a curvature per voxel from its neighbours within R metres "
+                        "(32-byte records with normal_x, normal_y, normal_z, curvature; PCL's NormalEstimation with a "
+                        "radius search; 0.02..4, between the largest leaf and 4 times the smallest; default: off)")
 
 
 def voxel_options(flags, error=None):
@@ -654,7 +658,7 @@ def voxel_options(flags, error=None):
         raise ValueError(msg)
 
     if not flags.voxel_topic:
-        for attr in ("voxel_leaf", "voxel_min_points"):
+        for attr in ("voxel_leaf", "voxel_min_points", "voxel_normals"):
             if getattr(flags, attr) is not None:
                 fail(f"--{attr.replace('_', '-')} needs --voxel-topic TOPIC")
         return None
@@ -671,10 +675,13 @@ def voxel_options(flags, error=None):
         kw["leaf"] = sides[0] if len(sides) == 1 else sides
     if flags.voxel_min_points is not None:
         kw["min_points"] = flags.voxel_min_points
+    if flags.voxel_normals is not None:
+        kw["normal_radius"] = flags.voxel_normals
+    names = {"leaf": "--voxel-leaf", "min_points": "--voxel-min-points", "normal_radius": "--voxel-normals"}
     try:
         return VoxelOptions(**kw)
     except ValueError as e:
-        fail(f"{ {'leaf': '--voxel-leaf', 'min_points': '--voxel-min-points'}.get(str(e).split()[0], '--voxel-topic')}: {e}")
+        fail(f"{names.get(str(e).split()[0], '--voxel-topic')}: {e}")
 
 
 def bev_view(engine, res: float, enabled):

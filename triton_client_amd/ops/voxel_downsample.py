@@ -34,8 +34,18 @@ without a sort.
 Two departures from PCL's ``VoxelGrid``: PCL sums in float in input order and sorts the output by
 voxel index (here: integer sums, first-point order), and every other field (ring, time) is dropped.
 
+**Normals** (``VoxelOptions.normal_radius``, off by default; K35).  With a radius the record grows
+by a surface normal and a curvature per voxel, what PCL's ``NormalEstimation`` with a radius search
+computes behind a ``VoxelGrid``.  :func:`normals_numpy` is the definition, a function of the
+published float32 centroids alone: quantised coordinates, a closed ball in int64, integer moments
+about the voxel itself, a float64 covariance rounded to float32 and a fixed number of float32
+Jacobi sweeps (``docs/precision.md`` has the rotation's operation order).  ``tca_voxel_normals``
+(``csrc/kernels/voxel_normals.hip``) gives its bytes on the device behind ``tca_voxel_downsample``,
+and :func:`normals_ref` is a float64 brute force with ``np.linalg.eigh``.
+
 Not here: averaging or carrying the other fields, ``filter_field_name`` limits and ``leaf_layout``,
-feeding the thinned cloud into the detectors or the other side outputs, tf.
+feeding the thinned cloud into the detectors or the other side outputs, tf, k-nearest search,
+viewpoints other than the origin, normals of the unthinned cloud.
 """
 from __future__ import annotations
 
@@ -63,9 +73,14 @@ QC, QI = 65536, 4096  # units per metre of the coordinate sums, per unit of the 
 I_LIMIT = 65536.0  # an intensity is clamped to this in magnitude
 SLOT = 48  # bytes of a table slot: key, four int64 sums, count, first point
 BLOCK = 256  # points per block of the device's counts
-RECORD = 16  # bytes of an output record
+RECORD = 16  # bytes of an output record, and of a voxel's normal and curvature
+RADIUS_MIN, RADIUS_MAX = 0.02, 4.0  # of the normals' ball, metres
+RADIUS_LEAVES = 4  # the ball's radius is at most this many of the smallest leaf: at most 10^3 neighbours
+SWEEPS = 4  # cyclic Jacobi sweeps of the normals' eigen-solve (docs/precision.md)
+CELL_SLOT = 16  # bytes of a slot of the normals' cell table: key, count, start
 # The launch's variants as they are run (``profiles/voxel_downsample/README.md`` has the measurements).
 DEFAULTS = {"wave": True, "lds": True, "saved": True}
+NORMALS_DEFAULTS = {"stage": False}  # (``profiles/voxel_normals/README.md``)
 
 
 def device_enabled() -> bool:
@@ -78,6 +93,7 @@ def device_enabled() -> bool:
 class VoxelOptions:
     leaf: object = 0.2  # one number, or (lx, ly, lz)
     min_points: int = 1
+    normal_radius: float = 0.0  # metres; 0: no normals
 
     def __post_init__(self):
         v = self.leaf
@@ -92,6 +108,23 @@ class VoxelOptions:
                 raise ValueError(f"leaf must lie within {LEAF_MIN}..{LEAF_MAX:g} m on every axis, got {v!r}")
         object.__setattr__(self, "leaf", sides)
         C._count("min_points", self.min_points, 1, 2 ** 31 - 1)
+        r = _number("normal_radius", self.normal_radius)
+        if r != 0:
+            if not np.float32(RADIUS_MIN) <= np.float32(r) <= np.float32(RADIUS_MAX):
+                raise ValueError(f"normal_radius must be 0 (off) or lie within {RADIUS_MIN}..{RADIUS_MAX:g} m, got {r!r}")
+            if not max(self.l32) <= np.float32(r) <= np.float32(RADIUS_LEAVES) * min(self.l32):
+                raise ValueError(f"normal_radius must lie between the largest leaf and {RADIUS_LEAVES} times the smallest "
+                                 f"({max(sides):g}..{RADIUS_LEAVES * min(sides):g} m), got {r!r}")
+        object.__setattr__(self, "normal_radius", r)
+
+    @property
+    def normals(self) -> bool:
+        return self.normal_radius > 0
+
+    @property
+    def radius_q(self) -> int:
+        """The ball's radius in units of 2^-16 m."""
+        return int(np.rint(np.float32(self.normal_radius) * np.float32(QC)))
 
     @property
     def l32(self) -> Tuple[np.float32, np.float32, np.float32]:
@@ -200,22 +233,158 @@ def downsample_ref(points, opts: VoxelOptions):
     return np.array(mean, np.float64).reshape(-1, 4), np.array([k for k, _ in kept], np.int64), band
 
 
+# ----------------------------------------------------------------------------- normals
+NAN_ROW = np.full(4, np.uint32(0x7FC00000)).view(np.float32)  # a voxel with fewer than three neighbours
+
+
+def _pairs(q: np.ndarray, R: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Every ordered pair ``(a, b)`` of rows of ``q`` (int64 [K, 3]) whose cells of side ``R`` touch —
+    a superset of the pairs within ``R`` — grouped by ``a``.  The cell index is a floor division."""
+    cell = q // R + BIAS
+    key = (cell[:, 2] << 42) | (cell[:, 1] << 21) | cell[:, 0]
+    order = np.argsort(key, kind="stable")
+    sk = key[order]
+    a_all, b_all = [], []
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                want = key + ((dz << 42) + (dy << 21) + dx)
+                lo, hi = np.searchsorted(sk, want, "left"), np.searchsorted(sk, want, "right")
+                n = hi - lo
+                a = np.repeat(np.arange(len(q)), n)
+                a_all.append(a)
+                b_all.append(order[np.arange(len(a)) - np.repeat(np.cumsum(n) - n, n) + lo[a]])
+    return np.concatenate(a_all), np.concatenate(b_all)
+
+
+def moments_numpy(rows, opts: VoxelOptions) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The integer half of the normals' definition → ``(m [K], Sd [K, 3], Sdd [K, 6])``, int64: per
+    voxel the neighbours of its closed ball (itself included), the sums of their offsets ``d`` and of
+    ``d_i d_j`` for ij = xx, xy, xz, yy, yz, zz, in units of 2^-16 m."""
+    c = _columns(rows)[:, :3]
+    q = np.rint(c * np.float32(QC)).astype(np.int64)
+    R = opts.radius_q
+    a, b = _pairs(q, R)
+    d = q[b] - q[a]
+    near = (d * d).sum(1) <= R * R
+    a, d = a[near], d[near]
+    K = len(q)
+    # (float64 weights are exact here: every partial sum is an integer below 2^46)
+    tot = lambda w: np.bincount(a, w.astype(np.float64), K).astype(np.int64)
+    m = np.bincount(a, minlength=K).astype(np.int64)
+    Sd = np.stack([tot(d[:, i]) for i in range(3)], 1).reshape(K, 3)
+    Sdd = np.stack([tot(d[:, i] * d[:, j]) for i, j in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))], 1).reshape(K, 6)
+    return m, Sd, Sdd
+
+
+def _rotate(app, aqq, apq, arp, arq, vp, vq):
+    """One Jacobi rotation of the pair (p, q) on float32 arrays, every operation rounded on its own
+    (``docs/precision.md``); where ``apq`` is exactly 0 nothing changes."""
+    one, skip = np.float32(1), apq == 0
+    with np.errstate(all="ignore"):
+        theta = (aqq - app) / (apq + apq)
+        t = np.where(theta < 0, -one, one) / (np.abs(theta) + np.sqrt(theta * theta + one))  # 0 for an infinite theta
+        c = one / np.sqrt(t * t + one)
+        s = t * c
+        h = t * apq
+        new = [app - h, aqq + h, np.zeros_like(apq), c * arp - s * arq, s * arp + c * arq,
+               c[:, None] * vp - s[:, None] * vq, s[:, None] * vp + c[:, None] * vq]
+    old = [app, aqq, apq, arp, arq, vp, vq]
+    return [np.where(skip if o.ndim == 1 else skip[:, None], o, n) for o, n in zip(old, new)]
+
+
+def eigen_numpy(cov: np.ndarray, sweeps: int = SWEEPS) -> Tuple[np.ndarray, np.ndarray]:
+    """Cyclic Jacobi in float32 on ``cov`` [K, 6] (xx, xy, xz, yy, yz, zz) → ``(diagonal [K, 3],
+    vectors [K, 3, 3])``, column j of ``vectors`` belonging to entry j of the diagonal.  The pairs of
+    a sweep are (0, 1), (0, 2), (1, 2)."""
+    a00, a01, a02, a11, a12, a22 = (cov[:, j].astype(np.float32) for j in range(6))
+    K = len(cov)
+    v0, v1, v2 = (np.tile(np.eye(3, dtype=np.float32)[j], (K, 1)) for j in range(3))  # the columns
+    for _ in range(sweeps):
+        a00, a11, a01, a02, a12, v0, v1 = _rotate(a00, a11, a01, a02, a12, v0, v1)
+        a00, a22, a02, a01, a12, v0, v2 = _rotate(a00, a22, a02, a01, a12, v0, v2)
+        a11, a22, a12, a01, a02, v1, v2 = _rotate(a11, a22, a12, a01, a02, v1, v2)
+    return np.stack([a00, a11, a22], 1), np.stack([v0, v1, v2], 2)
+
+
+def normals_numpy(rows, opts: VoxelOptions, sweeps: int = SWEEPS) -> np.ndarray:
+    """The normals' definition → ``float32 [K, 4]`` (normal_x, normal_y, normal_z, curvature) of one
+    cloud's rows ``[K, >=3]``; four quiet NaNs for a voxel with fewer than three neighbours."""
+    c = np.ascontiguousarray(_columns(rows)[:, :3])
+    if not len(c):
+        return np.zeros((0, 4), np.float32)
+    m, Sd, Sdd = moments_numpy(c, opts)
+    fm, fd = m.astype(np.float64), Sd.astype(np.float64)
+    ij = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+    cov = np.stack([Sdd[:, k].astype(np.float64) - (fd[:, i] * fd[:, j]) / fm for k, (i, j) in enumerate(ij)], 1)
+    lam, vec = eigen_numpy(cov.astype(np.float32), sweeps)
+    low = np.argmin(lam, 1)  # (the first of equal entries)
+    n = vec[np.arange(len(c)), :, low]
+    with np.errstate(all="ignore"):
+        n = n / np.sqrt(n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2])[:, None]
+        away = n[:, 0] * c[:, 0] + n[:, 1] * c[:, 1] + n[:, 2] * c[:, 2] > 0
+        n = np.where(away[:, None], -n, n)
+        total = lam[:, 0] + lam[:, 1] + lam[:, 2]
+        least = lam[np.arange(len(c)), low]
+        least = np.where(least < 0, np.float32(0), least)
+        curv = np.where(total > 0, least / total, np.float32(0))
+    out = np.concatenate([n, curv[:, None]], 1).astype(np.float32)
+    out[m < 3] = NAN_ROW
+    return out
+
+
+def normals_ref(rows, opts: VoxelOptions, g: float = 0.05):
+    """Float64 brute force with nothing of the definition's code → ``(normals float64 [K, 4], m int64
+    [K], odd bool [K], flat bool [K])``: pairwise distances on ``float64(rows)`` against
+    ``float64(float32(r))``, the plain covariance about the neighbours' mean, ``np.linalg.eigh``.
+    ``odd``: a pair of the voxel lies within 2^-14 m of the radius (a ``rint`` moves a coordinate by at
+    most 2^-17 m, a distance by at most sqrt(3) 2^-16 m), so the quantised ball may hold another set;
+    ``flat``: fewer than three neighbours, or ``(l1 - l0) < g l2``: no well-conditioned normal."""
+    p = np.asarray(rows, np.float32)
+    p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 3)[:, :3].astype(np.float64)
+    r = float(np.float32(opts.normal_radius))
+    K = len(p)
+    out, m = np.full((K, 4), np.nan), np.zeros(K, np.int64)
+    odd, flat = np.zeros(K, bool), np.ones(K, bool)
+    for a in range(K):
+        dist = np.sqrt(((p - p[a]) ** 2).sum(1))
+        odd[a] = (np.abs(dist - r) <= 2.0 ** -14).any()
+        nb = p[dist <= r]
+        m[a] = len(nb)
+        if len(nb) < 3:
+            continue
+        e = nb - nb.mean(0)
+        lam, vec = np.linalg.eigh(e.T @ e)
+        n = vec[:, 0] if vec[:, 0] @ p[a] <= 0 else -vec[:, 0]
+        out[a] = [*n, max(lam[0], 0.0) / lam.sum() if lam.sum() > 0 else 0.0]
+        flat[a] = (lam[1] - lam[0]) < g * lam[2]
+    return out, m, odd, flat
+
+
 # ---------------------------------------------------------------------------- messages
 def downsample_message(cloud, rows: np.ndarray) -> msgs.PointCloud2:
-    """The rows as an unorganised, dense, little-endian ``PointCloud2`` of 16-byte records with the
-    cloud's header: FLOAT32 x, y, z at 0, 4, 8 and, when the input cloud has one, ``intensity`` at
-    12 (the dword is there either way)."""
-    a = np.ascontiguousarray(rows, "<f4").reshape(-1, 4)
+    """The rows as an unorganised, little-endian ``PointCloud2`` with the cloud's header.  Rows of
+    four columns: 16-byte records, FLOAT32 x, y, z at 0, 4, 8 and, when the input cloud has one,
+    ``intensity`` at 12 (the dword is there either way), dense.  Rows of eight (normals on): 32-byte
+    records with FLOAT32 ``normal_x``, ``normal_y``, ``normal_z``, ``curvature`` at 16, 20, 24, 28
+    behind them, and ``is_dense`` False when a voxel has no normal (NaNs)."""
+    a = np.ascontiguousarray(rows, "<f4")
+    a = a.reshape(-1, a.shape[-1] if a.ndim > 1 and a.shape[-1] == 8 else 4)
+    step = 4 * a.shape[1]
     fields = [msgs.PointField("x", 0, 7, 1), msgs.PointField("y", 4, 7, 1), msgs.PointField("z", 8, 7, 1)]
     if any(f.name == "intensity" for f in cloud.fields):
         fields.append(msgs.PointField("intensity", 12, 7, 1))
+    if step > RECORD:
+        fields += [msgs.PointField(n, RECORD + 4 * j, 7, 1) for j, n in enumerate(("normal_x", "normal_y", "normal_z", "curvature"))]
+    dense = step == RECORD or not bool(np.isnan(a[:, 4:]).any())
     return msgs.PointCloud2(header=cloud.header, height=1, width=len(a), fields=fields, is_bigendian=False,
-                            point_step=RECORD, row_step=RECORD * len(a), data=a.tobytes(), is_dense=True)
+                            point_step=step, row_step=step * len(a), data=a.tobytes(), is_dense=dense)
 
 
 def downsample_cloud_numpy(cloud, opts: VoxelOptions, lay: Optional[CloudLayout] = None) -> np.ndarray:
-    """One cloud through the definition → its rows."""
-    return downsample_numpy(cloud_xyzi(cloud, lay), opts)
+    """One cloud through the definition → its rows, ``[K, 8]`` with normals on."""
+    rows = downsample_numpy(cloud_xyzi(cloud, lay), opts)
+    return np.concatenate([rows, normals_numpy(rows, opts)], 1) if opts.normals else rows
 
 
 # --------------------------------------------------------------------------------- GPU
@@ -263,6 +432,7 @@ class VoxelCall:
     ns: Tuple[int, ...]
     slots: Tuple[int, ...]
     opts: VoxelOptions
+    normals: Optional[torch.Tensor] = None  # uint8, with normals on: 16 bytes per record at the record's index
 
     @property
     def table_bytes(self) -> int:
@@ -290,11 +460,14 @@ class VoxelCall:
 
 
 def launch(c: VoxelCall, stream=None, wave: Optional[bool] = None, lds: Optional[bool] = None,
-           saved: Optional[bool] = None) -> None:
-    """The launch alone (five kernels on ``stream``): no allocation, no copy, no sync.  ``wave``:
+           saved: Optional[bool] = None, stage: Optional[bool] = None) -> None:
+    """The launch alone (five kernels on ``stream``, and with normals on the five of
+    ``tca_voxel_normals`` behind them): no allocation, no copy, no sync.  ``wave``:
     runs of equal voxels of a wave are reduced with shuffles first; ``lds``: a workgroup gathers its
     span of points in a table in LDS; ``saved``: the scatter reads the slot the count pass kept
-    instead of probing the table again.  None: :data:`DEFAULTS`."""
+    instead of probing the table again.  None: :data:`DEFAULTS`.  ``stage``: the normals' fit stages
+    the candidates of a cell's 27 neighbours through LDS once per cell instead of every lane probing
+    and reading for itself (measured slower on the sweep: off); None: :data:`NORMALS_DEFAULTS`."""
     wave, lds, saved = (DEFAULTS[k] if v is None else v for k, v in (("wave", wave), ("lds", lds), ("saved", saved)))
     p = _native.ptr
     o, r = c.layout.offsets, c.opts
@@ -304,6 +477,20 @@ def launch(c: VoxelCall, stream=None, wave: Optional[bool] = None, lds: Optional
                  int(r.min_points), 1 if wave else 0, 1 if lds else 0, 1 if saved else 0, p(c.table), c.table_bytes,
                  p(c.memo), c.memo_bytes, p(c.blocks), c.blocks_bytes, p(c.out), c.rows_bytes, p(c.counts),
                  _native.stream_ptr(stream))
+    if r.normals:
+        launch_normals(c, stream, stage)
+
+
+def launch_normals(c: VoxelCall, stream=None, stage: Optional[bool] = None) -> None:
+    """``tca_voxel_normals`` alone, behind a ``tca_voxel_downsample`` of the same call on ``stream``: it
+    reads the records and the counts on the device, and the leaf table, dead after the scatter, is
+    the cell lists' workspace."""
+    stage = NORMALS_DEFAULTS["stage"] if stage is None else stage
+    p = _native.ptr
+    ns, slots = np.asarray(c.ns, np.int32), np.asarray(c.slots, np.int32)
+    _native.call("tca_voxel_normals", p(c.out), c.rows_bytes, p(c.counts), ns.ctypes.data, slots.ctypes.data,
+                 c.batch, c.opts.radius_q, 1 if stage else 0, p(c.table), c.table_bytes, p(c.normals), c.rows_bytes,
+                 _native.stream_ptr(stream))
 
 
 def layout_device_ok(lay: CloudLayout) -> bool:
@@ -312,13 +499,16 @@ def layout_device_ok(lay: CloudLayout) -> bool:
     return fields_f32(lay, (0, 1, 2, 3) if lay.offsets[3] >= 0 else (0, 1, 2))
 
 
-def rows_of(host: np.ndarray, c: VoxelCall) -> List[np.ndarray]:
-    """Per cloud its rows ``float32 [K, 4]`` (copies) of a launch's output bytes (``out_bytes`` of them)."""
+def rows_of(host: np.ndarray, c: VoxelCall, normals: Optional[np.ndarray] = None) -> List[np.ndarray]:
+    """Per cloud its rows ``float32 [K, 4]`` (copies) of a launch's output bytes (``out_bytes`` of them);
+    with the bytes of its normals (``rows_bytes`` of them), ``[K, 8]``."""
     counts = host[c.rows_bytes:c.out_bytes].view("<i4")
     res, at = [], 0
     for b, n in enumerate(c.ns):
         k = int(counts[b])
-        res.append(host[RECORD * at:RECORD * (at + k)].view("<f4").reshape(k, 4).copy())
+        cut = slice(RECORD * at, RECORD * (at + k))
+        rows = host[cut].view("<f4").reshape(k, 4)
+        res.append(rows.copy() if normals is None else np.concatenate([rows, normals[cut].view("<f4").reshape(k, 4)], 1))
         at += n
     return res
 
@@ -331,7 +521,7 @@ class VoxelDownsampler(CloudStager):
     big-endian x, y, z, an intensity that is present but not FLOAT32) run the definition with one
     warning.  ``wave``, ``lds``, ``saved``: the launch's variants, None for :data:`DEFAULTS`."""
 
-    wave = lds = saved = None
+    wave = lds = saved = stage = None
 
     def prepare(self, payloads: Sequence, ns: Sequence[int], layout: CloudLayout, opts: VoxelOptions, stream=None,
                 misalign: int = 0, slots: Optional[Sequence[int]] = None) -> VoxelCall:
@@ -362,14 +552,19 @@ class VoxelDownsampler(CloudStager):
         c.memo = self._device_buf("voxel_memo", c.memo_bytes)
         c.blocks = self._device_buf("voxel_blocks", c.blocks_bytes)
         c.out = self._device_buf("voxel_out", c.out_bytes)
+        if opts.normals:
+            c.normals = self._device_buf("voxel_normals", c.rows_bytes)
         return c
 
     launch = staticmethod(launch)
 
-    def _fetch_counted(self, c: VoxelCall, st) -> np.ndarray:
-        """The counts, a synchronize, then only the used records of every cloud's slot; the host
-        bytes are laid out like the output."""
-        pin = self._pinned("_pin_out", c.out_bytes)
+    def _fetch_counted(self, c: VoxelCall, st) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """The counts, a synchronize, then only the used records of every cloud's slot, and with
+        normals on the same parts of the normals → the host bytes, laid out like the output, and the
+        normals' (None when off)."""
+        on = c.normals is not None
+        pin = self._pinned("_pin_out", _align(c.out_bytes) + c.rows_bytes if on else c.out_bytes)
+        side = pin[_align(c.out_bytes):] if on else None
         with torch.cuda.stream(st):
             pin[c.rows_bytes:c.out_bytes].copy_(c.out[c.rows_bytes:c.out_bytes], non_blocking=True)
         st.synchronize()
@@ -380,21 +575,25 @@ class VoxelDownsampler(CloudStager):
                 lo, hi = RECORD * at, RECORD * (at + int(counts[b]))
                 if hi > lo:
                     pin[lo:hi].copy_(c.out[lo:hi], non_blocking=True)
+                    if on:
+                        side[lo:hi].copy_(c.normals[lo:hi], non_blocking=True)
                 at += n
         st.synchronize()
-        return pin.numpy()[:c.out_bytes]
+        return pin.numpy()[:c.out_bytes], side.numpy()[:c.rows_bytes] if on else None
 
     def _run_device(self, payloads, ns, layout, opts):
         """→ per frame its rows."""
         with torch.cuda.device(self.device):
             st = self._own_stream()
             c = self.prepare(payloads, ns, layout, opts, st)
-            launch(c, st, self.wave, self.lds, self.saved)
-            return rows_of(self._fetch_counted(c, st), c)
+            launch(c, st, self.wave, self.lds, self.saved, self.stage)
+            host, normals = self._fetch_counted(c, st)
+            return rows_of(host, c, normals)
 
     # ---------------------------------------------------------------------- API
     def downsample(self, clouds: Sequence, opts: VoxelOptions) -> List[np.ndarray]:
-        """Per cloud its rows ``float32 [K, 4]``, in input order."""
+        """Per cloud its rows ``float32 [K, 4]``, in input order; ``[K, 8]`` with ``opts.normal_radius``:
+        normal x, y, z and curvature behind them (``tca_voxel_normals`` in the same launch group)."""
         return self._per_cloud(
             clouds, lambda i, lay: layout_device_ok(lay),
             lambda i, lay: downsample_cloud_numpy(clouds[i], opts, lay),
