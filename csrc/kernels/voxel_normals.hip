@@ -11,23 +11,10 @@
 // towards the origin, and max(l_min, 0) / (l0 + l1 + l2).  m < 3: four quiet NaNs.
 //
 // After the scatter of tca_voxel_downsample its leaf table (48 bytes a slot, slots[b] >= the cloud's points) is dead;
-// its bytes are this launch's workspace:
+// its bytes are this launch's workspace: the cell lists of side R, which tca_cell_lists.h builds (reset, keys, starts,
+// sort; K36's outlier filter builds the same).  (slot, rank) of the keys pass wait in the row's 16 bytes of the output,
+// which the fit overwrites last.
 //
-//     cells   16 bytes a slot, slots[b] per cloud: key int64 | count int32 | start int32, open addressing, linear
-//             probing; the key packs the three cell indices (21 bits each), -1 is empty.  A cell has the side R and its
-//             index is the FLOOR of q / R (-1 and +1 lie in different cells), so every neighbour of a voxel lies in
-//             the 27 cells around its own, exactly.
-//     sorted  16 bytes a record, the cloud's records one cell after the other: qx, qy, qz, row.
-//     cursor  int32 per cloud.
-//
-//   reset   every cell slot empty, every cursor 0.
-//   keys    a row claims its cell's slot (one 64-bit compare-and-swap); its atomicAdd on the slot's count is its rank
-//           inside the cell.  (slot, rank) wait in the row's 16 bytes of the output, which the fit overwrites last.
-//   starts  every slot takes its cell's first record from the cloud's cursor: a wave adds its 64 counts with shuffles
-//           and advances the cursor once.  A per-cloud prefix in slot order would do the same with one workgroup
-//           walking slots[b] slots; the cursor spreads that over the device at the price of an order of the cells that
-//           depends on who won the atomics, like the order inside a cell.
-//   sort    a row stores its quad at start + rank.
 //   fit     one lane per record in cell order, one wave per workgroup.  stage = 1: the wave loops over the distinct
 //           cells among its lanes (a ballot, the first lane's cell broadcast); lanes 0..26 probe the 27 cells around it
 //           — 27 probes per cell, not per row — a shuffle scan turns their counts into one run of candidates, which
@@ -39,7 +26,7 @@
 // No workgroup waits on another, only integer atomics are used, the resets belong to the launch (a relaunch or a graph
 // replay gives the same bytes), nothing is allocated and no hipMemset is used.  Contraction to FMA is switched off for
 // this file; division and square root are IEEE.
-#include "tca_common.h"
+#include "tca_cell_lists.h"
 
 #include <cmath>
 
@@ -49,143 +36,10 @@ using namespace tca;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kMaxFrames = 64;
-constexpr int kMaxPoints = 1 << 24;
-constexpr int kBias = 1 << 20;
 constexpr int kSweeps = 4;  // ops/voxel_downsample.py SWEEPS
-constexpr int kMaxRadius = 4 << 16;
-constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr unsigned kNaN = 0x7FC00000u;
 
-struct Cell {  // 16 bytes
-  unsigned long long key;
-  int count, start;
-};
-static_assert(sizeof(Cell) == 16, "a cell slot is 16 bytes");
-
-struct NormalArgs {
-  int radius;                 // R, units of 2^-16 m
-  int max_n;
-  int n[kMaxFrames];          // the points of cloud b the host knows: the most records it has
-  int pt_off[kMaxFrames];     // the records before cloud b's
-  int mask[kMaxFrames];       // slots[b] - 1
-  long slot_off[kMaxFrames];  // the slots before cloud b's
-};
-
-__device__ __forceinline__ int records_of(const int* __restrict__ counts, const NormalArgs& a, int b) {
-  return min(max(counts[b], 0), a.n[b]);
-}
-
-__device__ __forceinline__ int quantise(unsigned bits) {
-  const float v = __uint_as_float(bits);
-  return fabsf(v) <= 512.f ? (int)rintf(v * 65536.f) : 0;  // (a record of tca_voxel_downsample always is)
-}
-
-__device__ __forceinline__ int floor_div(int q, int r) {
-  const int d = q / r;
-  return (q % r != 0 && q < 0) ? d - 1 : d;
-}
-
-__device__ __forceinline__ unsigned long long cell_key(int cx, int cy, int cz) {
-  return ((unsigned long long)(cz + kBias) << 42) | ((unsigned long long)(cy + kBias) << 21) |
-         (unsigned long long)(cx + kBias);
-}
-
-__device__ __forceinline__ unsigned hash_of(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return (unsigned)k;
-}
-
-// The records of cell `key`: where they start and how many, 0 if the cell is empty or the run is not inside [0, K).
-__device__ __forceinline__ int find_cell(const Cell* __restrict__ tab, int mask, unsigned long long key, int K,
-                                         int* start) {
-  unsigned h = hash_of(key) & (unsigned)mask;
-  for (int probe = 0; probe <= mask; ++probe, h = (h + 1u) & (unsigned)mask) {
-    const unsigned long long seen = tab[h].key;
-    if (seen == kEmptyKey) return 0;
-    if (seen == key) {
-      const int s = tab[h].start, n = tab[h].count;
-      *start = s;
-      return (s >= 0 && n > 0 && n <= K && s <= K - n) ? n : 0;
-    }
-  }
-  return 0;
-}
-
-__global__ void __launch_bounds__(kBlock) normals_reset_kernel(uint4* __restrict__ cells, long n_slots,
-                                                               int* __restrict__ cursor, int batch) {
-  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
-  if (i < n_slots) cells[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-  else if (i < n_slots + batch) cursor[i - n_slots] = 0;
-}
-
-__global__ void __launch_bounds__(kBlock) normals_keys_kernel(const uint4* __restrict__ rows,
-                                                              const int* __restrict__ counts, NormalArgs a,
-                                                              Cell* __restrict__ cells, uint4* __restrict__ scratch) {
-  const int b = blockIdx.y;
-  const int K = records_of(counts, a, b);
-  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= K) return;
-  const uint4 rec = rows[a.pt_off[b] + i];
-  const unsigned long long key = cell_key(floor_div(quantise(rec.x), a.radius), floor_div(quantise(rec.y), a.radius),
-                                          floor_div(quantise(rec.z), a.radius));
-  Cell* tab = cells + a.slot_off[b];
-  const int mask = a.mask[b];
-  int slot = -1, rank = 0;
-  unsigned h = hash_of(key) & (unsigned)mask;
-  // at most K <= slots[b] distinct cells: the probe ends at the key or at an empty slot
-  for (int probe = 0; probe <= mask; ++probe, h = (h + 1u) & (unsigned)mask) {
-    unsigned long long seen = tab[h].key;  // (a key never changes once it is set)
-    if (seen == kEmptyKey) seen = atomicCAS(&tab[h].key, kEmptyKey, key);
-    if (seen == kEmptyKey || seen == key) {
-      slot = (int)h;
-      rank = atomicAdd(&tab[h].count, 1);
-      break;
-    }
-  }
-  scratch[a.pt_off[b] + i] = make_uint4((unsigned)slot, (unsigned)rank, 0u, 0u);
-}
-
-__global__ void __launch_bounds__(kBlock) normals_starts_kernel(NormalArgs a, Cell* __restrict__ cells,
-                                                                int* __restrict__ cursor) {
-  const int b = blockIdx.y;
-  const long s = (long)blockIdx.x * kBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const bool in = s <= a.mask[b];
-  Cell* tab = cells + a.slot_off[b];
-  const int own = in ? tab[s].count : 0;
-  int upto = own;  // the wave's inclusive prefix (every lane of the wave is here: no early return above)
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(upto, o, 64);
-    if (lane >= o) upto += t;
-  }
-  int base = 0;
-  if (lane == 63 && upto > 0) base = atomicAdd(&cursor[b], upto);
-  base = __shfl(base, 63, 64);
-  if (in) tab[s].start = base + upto - own;
-}
-
-__global__ void __launch_bounds__(kBlock) normals_sort_kernel(const uint4* __restrict__ rows,
-                                                              const int* __restrict__ counts, NormalArgs a,
-                                                              const Cell* __restrict__ cells,
-                                                              const uint4* __restrict__ scratch, int4* __restrict__ sorted) {
-  const int b = blockIdx.y;
-  const int K = records_of(counts, a, b);
-  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= K) return;
-  const uint4 rec = rows[a.pt_off[b] + i];
-  const uint4 sr = scratch[a.pt_off[b] + i];
-  const int slot = (int)sr.x, rank = (int)sr.y;
-  if (slot < 0 || slot > a.mask[b] || rank < 0) return;  // (never: the keys pass wrote it)
-  const long pos = (long)cells[a.slot_off[b] + slot].start + rank;
-  if (pos >= 0 && pos < K) sorted[a.pt_off[b] + pos] = make_int4(quantise(rec.x), quantise(rec.y), quantise(rec.z), (int)i);
-}
+using NormalArgs = CellArgs;
 
 struct Moments {
   int m, sd[3];
@@ -338,57 +192,22 @@ __global__ void __launch_bounds__(64) normals_fit_kernel(const uint4* __restrict
 TCA_API int tca_voxel_normals(const void* rows, long rows_bytes, const int* counts, const int* ns, const int* slots,
                               int batch, int radius_q, int stage, void* table, long table_bytes, void* normals,
                               long normals_bytes, hipStream_t stream) {
-  if (batch < 1 || batch > kMaxFrames || ns == nullptr || slots == nullptr || radius_q < 1 || radius_q > kMaxRadius ||
-      (stage != 0 && stage != 1))
+  CellPlan p;
+  if ((stage != 0 && stage != 1) || !cell_plan(ns, slots, batch, radius_q, 0, table, table_bytes, p))
     return (int)hipErrorInvalidValue;
-  NormalArgs a;
-  long n_sum = 0, slot_sum = 0;
-  int max_n = 0, max_slots = 0;
-  for (int b = 0; b < batch; ++b) {
-    const int n = ns[b], s = slots[b];
-    if (n < 0 || n > kMaxPoints || s < 2 || s < n || (s & (s - 1)) != 0) return (int)hipErrorInvalidValue;
-    a.n[b] = n;
-    a.mask[b] = s - 1;
-    a.pt_off[b] = (int)n_sum;
-    a.slot_off[b] = slot_sum;
-    n_sum += n;
-    slot_sum += s;
-    max_n = n > max_n ? n : max_n;
-    max_slots = s > max_slots ? s : max_slots;
-    if (n_sum >= 0x80000000L / 16) return (int)hipErrorInvalidValue;
-  }
-  // cells, sorted and cursor fit the leaf table: 16 (slots + n) + 4 B <= 34 slots
-  if (table_bytes < 48 * slot_sum || rows_bytes < 16 * n_sum || normals_bytes < 16 * n_sum)
+  if (rows_bytes < 16 * p.n_sum || normals_bytes < 16 * p.n_sum) return (int)hipErrorInvalidValue;
+  if (rows == nullptr || counts == nullptr || normals == nullptr) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)rows & 15) != 0 || ((uintptr_t)normals & 15) != 0 || ((uintptr_t)counts & 3) != 0)
     return (int)hipErrorInvalidValue;
-  if (rows == nullptr || counts == nullptr || table == nullptr || normals == nullptr)
-    return (int)hipErrorInvalidValue;
-  if (((uintptr_t)rows & 15) != 0 || ((uintptr_t)table & 15) != 0 || ((uintptr_t)normals & 15) != 0 ||
-      ((uintptr_t)counts & 3) != 0)
-    return (int)hipErrorInvalidValue;
-  if (max_n == 0) return (int)hipSuccess;
-  a.radius = radius_q;
-  a.max_n = max_n;
+  if (p.a.max_n == 0) return (int)hipSuccess;
 
-  Cell* cells = (Cell*)table;
-  int4* sorted = (int4*)((uint8_t*)table + 16 * slot_sum);
-  int* cursor = (int*)((uint8_t*)table + 16 * (slot_sum + n_sum));
   const uint4* in = (const uint4*)rows;
   uint4* out = (uint4*)normals;
-  const int nblk = (max_n + kBlock - 1) / kBlock;
-
-  normals_reset_kernel<<<(unsigned)((slot_sum + batch + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
-      (uint4*)table, slot_sum, cursor, batch);
-  if (int e = (int)hipGetLastError()) return e;
-  normals_keys_kernel<<<dim3(nblk, batch), kBlock, 0, stream>>>(in, counts, a, cells, out);
-  if (int e = (int)hipGetLastError()) return e;
-  normals_starts_kernel<<<dim3((max_slots + kBlock - 1) / kBlock, batch), kBlock, 0, stream>>>(a, cells, cursor);
-  if (int e = (int)hipGetLastError()) return e;
-  normals_sort_kernel<<<dim3(nblk, batch), kBlock, 0, stream>>>(in, counts, a, cells, out, sorted);
-  if (int e = (int)hipGetLastError()) return e;
-  const dim3 grid((max_n + 63) / 64, batch);
+  if (int e = cell_lists_build(p, in, counts, batch, 0, out, stream)) return e;
+  const dim3 grid((p.a.max_n + 63) / 64, batch);
   if (stage)
-    normals_fit_kernel<true><<<grid, 64, 0, stream>>>(in, counts, a, cells, sorted, out, n_sum);
+    normals_fit_kernel<true><<<grid, 64, 0, stream>>>(in, counts, p.a, p.cells, p.sorted, out, p.n_sum);
   else
-    normals_fit_kernel<false><<<grid, 64, 0, stream>>>(in, counts, a, cells, sorted, out, n_sum);
+    normals_fit_kernel<false><<<grid, 64, 0, stream>>>(in, counts, p.a, p.cells, p.sorted, out, p.n_sum);
   TCA_LAUNCH_CHECK();
 }

@@ -3,6 +3,8 @@
     python tools/bench_voxel_downsample.py --clouds 32 --reps 20        # device events per leaf and variant, the checks
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_voxel_downsample.py --reps 20 --leaves 0.2 --variants default
 
+    python tools/bench_voxel_downsample.py --leaves 0.2 --variants default --outlier-radius 0.6 --outlier-neighbors 3 --outlier-mean-k 5,16
+
 Every variant's rows are compared with the first variant's on all clouds, and those with the definition on the first
 cloud.  The figure of a variant is its whole launch (five kernels), the median of `--reps` event-timed launches.
 Prints one JSON line.
@@ -46,6 +48,11 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip timing the host definition")
     ap.add_argument("--normals", type=float, default=0.0, metavar="R",
                     help="also time tca_voxel_normals alone at this radius, stage on and off, and check its bytes")
+    ap.add_argument("--outlier-radius", type=float, default=0.0, metavar="R",
+                    help="also time tca_voxel_outliers behind the downsample at this radius and check its bytes")
+    ap.add_argument("--outlier-neighbors", type=int, default=0, metavar="N")
+    ap.add_argument("--outlier-mean-k", default="", metavar="K[,K...]", help="one timing per K")
+    ap.add_argument("--outlier-stddev", type=float, default=1.0, metavar="A")
     a = ap.parse_args()
     from triton_client_amd.ops import voxel_downsample as V
     from triton_client_amd.ops.cloud_common import CloudLayout
@@ -89,6 +96,25 @@ def main():
                 "no_normal_share": round(float(np.mean([np.isnan(r[:, 4]).mean() for r in rows8 if len(r)])), 4),
                 **{f"stage_{'on' if s else 'off'}_us": {"median": round(v[len(v) // 2], 1), "min": round(v[0], 1),
                                                          "max": round(v[-1], 1)} for s, v in alone.items()}}
+        if a.outlier_radius:  # (the filter rewrites the counts, so it is timed behind a downsample: the difference is its own)
+            thin = V.downsample_numpy(clouds[0], V.VoxelOptions(leaf=leaf))
+            plain = timed(lambda: V.launch(V.VoxelCall(**{**call.__dict__, "opts": V.VoxelOptions(leaf=leaf)})), a.reps)
+            res = {"radius": a.outlier_radius, "downsample_alone_us": round(plain[len(plain) // 2], 1)}
+            for k in [int(t) for t in a.outlier_mean_k.split(",") if t] or [0]:
+                f = V.VoxelOptions(leaf=leaf, outlier_radius=a.outlier_radius, outlier_min_neighbors=a.outlier_neighbors,
+                                   outlier_mean_k=k, outlier_stddev=a.outlier_stddev)
+                both = op.prepare([c.tobytes() for c in clouds], [len(c) for c in clouds], lay, f)
+                t = timed(lambda: V.launch(both), a.reps)
+                got = V.rows_of(both.out[:both.out_bytes].cpu().numpy(), both, kept=both.kept[:both.rows_bytes].cpu().numpy())
+                t0 = time.perf_counter()
+                keep = V.outliers_numpy(thin, f)
+                host = round((time.perf_counter() - t0) * 1e3 * a.clouds, 1)
+                assert got[0].tobytes() == thin[keep].tobytes(), "not the outliers' definition's bytes"
+                res[f"k_{k}"] = {"with_downsample_us": {"median": round(t[len(t) // 2], 1), "min": round(t[0], 1), "max": round(t[-1], 1)},
+                                 "filter_us": round(t[len(t) // 2] - plain[len(plain) // 2], 1),
+                                 "removed_share": round(1 - sum(len(r) for r in got) / sum(len(r) for r in rows[first]), 4),
+                                 "numpy_ms_all_clouds_from_cloud0": host}
+            out[f"leaf_{leaf:g}"]["outliers"] = res
     print(json.dumps(out))
 
 

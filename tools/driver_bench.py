@@ -144,6 +144,12 @@ def main():
     ap.add_argument("--voxel-normals", type=float, default=0.0, metavar="R",
                     help="--voxel: with a normal and a curvature per voxel from its neighbours within R metres "
                          "(VoxelOptions.normal_radius; tca_voxel_normals)")
+    ap.add_argument("--voxel-outlier-radius", type=float, default=0.0, metavar="R",
+                    help="--voxel: with the outliers removed, the ball of the two tests below in metres "
+                         "(VoxelOptions.outlier_radius; tca_voxel_outliers)")
+    ap.add_argument("--voxel-outlier-neighbors", type=int, default=0, metavar="N", help="the radius test (outlier_min_neighbors)")
+    ap.add_argument("--voxel-outlier-mean-k", type=int, default=0, metavar="K", help="the statistical test (outlier_mean_k)")
+    ap.add_argument("--voxel-outlier-stddev", type=float, default=1.0, metavar="A", help="... and its outlier_stddev")
     ap.add_argument("--clusters-plain", action="store_true",
                     help="--clusters: one set of atomics per point instead of one per run of a wave (aggregate = 0)")
     ap.add_argument("--clusters-oriented", action="store_true",
@@ -267,6 +273,10 @@ def main():
                                             point_step=c.point_step, row_step=c.row_step, data=c.data,
                                             is_dense=True))
         st = _Stages()
+        vopts = {**({"normal_radius": a.voxel_normals} if a.voxel_normals else {}),
+                 **({"outlier_radius": a.voxel_outlier_radius, "outlier_min_neighbors": a.voxel_outlier_neighbors,
+                     "outlier_mean_k": a.voxel_outlier_mean_k, "outlier_stddev": a.voxel_outlier_stddev}
+                    if a.voxel_outlier_radius else {})}
         drv = RosInference3D(engine=eng3, params={"sub_topic": "/pc", "pub_topic": "/pc_out"}, bus=bus,
                              batch=a.batch, workers=a.workers, metrics=st, queue_size=window,
                              bev_topic="/pc_bev" if a.bev else None,
@@ -284,7 +294,7 @@ def main():
                              **({"grid_topic": "/pc_grid",
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.grid else {}),
                              **({"voxel_topic": "/pc_voxels"} if a.voxel else {}),
-                             **({"voxel_options": {"normal_radius": a.voxel_normals}} if a.voxel and a.voxel_normals else {}))
+                             **({"voxel_options": vopts} if a.voxel and vopts else {}))
         if a.clusters:
             from triton_client_amd.inference.engines import Detector3D
             extractor = Detector3D.cluster_extractor(eng3)
@@ -424,6 +434,10 @@ def main():
             out["lidar"]["output"] += f" + voxel cloud leaf {drv.voxel_options.leaf[0]:g} ({kind})"
             if drv.voxel_options.normals:
                 out["lidar"]["output"] += f" with normals r {drv.voxel_options.normal_radius:g}"
+            if drv.voxel_options.outliers:
+                o = drv.voxel_options
+                out["lidar"]["output"] += (f" less outliers r {o.outlier_radius:g} N {o.outlier_min_neighbors} "
+                                           f"k {o.outlier_mean_k} a {o.outlier_stddev:g}")
             out["lidar"]["voxel_downsampler"] = kind
             out["lidar"]["voxels"] = {"messages": len(thinned), "points_per_cloud": round(sum(thinned) / max(1, len(thinned)))}
         if a.tracks:

@@ -121,6 +121,11 @@ _KERNEL_SIGS = {
     # units of 2^-16 m, stage (0: every lane probes and reads for itself; 1: a cell's candidates go through LDS), the leaf table (now the cell lists'
     # workspace), its bytes, normals, their bytes, stream (csrc/kernels/voxel_normals.hip)
     "tca_voxel_normals": [P, L, P, P, P, I, I, I, P, L, P, L, P],
+    # tca_voxel_downsample's records, their bytes, its counts (rewritten: the survivors), ns and slots (HOST), B, the
+    # radius in units of 2^-16 m, min_neighbors (0: off), mean_k (0: off), stddev (double), the leaf table, the memo and
+    # the blocks of tca_voxel_downsample (now workspace) with their bytes, kept, its bytes, stream
+    # (csrc/kernels/voxel_outliers.hip)
+    "tca_voxel_outliers": [P, L, P, P, P, I, I, I, I, ctypes.c_double, P, L, P, L, P, L, P, L, P],
     # src, dst, map (int32 qx, qy per pixel, 16-byte aligned), H, W, n, stream (csrc/kernels/rectify.hip)
     "tca_rectify": [P, P, P, I, I, I, P],
     # the same with chunk (frames per read of a map entry) and byte_stores before the stream: measurements, tests

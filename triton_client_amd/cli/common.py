@@ -646,6 +646,24 @@ def add_voxel_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
                    help="also estimate a surface normal and a curvature per voxel from its neighbours within R metres "
                         "(32-byte records with normal_x, normal_y, normal_z, curvature; PCL's NormalEstimation with a "
                         "radius search; 0.02..4, between the largest leaf and 4 times the smallest; default: off)")
+    p.add_argument("--voxel-outlier-radius", type=float, default=None, metavar="R",
+                   help="remove outliers from the thinned cloud, in front of the normals: the radius in metres of the "
+                        "ball the two tests below search (0.02..4, between the largest leaf and 4 times the smallest; "
+                        "needs one of them; a voxel without a neighbour always goes; default: off)")
+    p.add_argument("--voxel-outlier-neighbors", type=int, default=None, metavar="N",
+                   help="keep a voxel with at least N neighbours within --voxel-outlier-radius (1..1000; PCL's "
+                        "RadiusOutlierRemoval)")
+    p.add_argument("--voxel-outlier-mean-k", type=int, default=None, metavar="K",
+                   help="keep a voxel whose mean distance to its K nearest neighbours within --voxel-outlier-radius is at "
+                        "most the cloud's mean + --voxel-outlier-stddev standard deviations (1..16; PCL's "
+                        "StatisticalOutlierRemoval, its search bounded by the ball)")
+    p.add_argument("--voxel-outlier-stddev", type=float, default=None, metavar="A",
+                   help="the standard deviations of --voxel-outlier-mean-k (default 1.0; 0..10)")
+
+
+_VOXEL_FLAGS = {"leaf": "--voxel-leaf", "min_points": "--voxel-min-points", "normal_radius": "--voxel-normals",
+                "outlier_radius": "--voxel-outlier-radius", "outlier_min_neighbors": "--voxel-outlier-neighbors",
+                "outlier_mean_k": "--voxel-outlier-mean-k", "outlier_stddev": "--voxel-outlier-stddev"}
 
 
 def voxel_options(flags, error=None):
@@ -658,7 +676,8 @@ def voxel_options(flags, error=None):
         raise ValueError(msg)
 
     if not flags.voxel_topic:
-        for attr in ("voxel_leaf", "voxel_min_points", "voxel_normals"):
+        for attr in ("voxel_leaf", "voxel_min_points", "voxel_normals", "voxel_outlier_radius", "voxel_outlier_neighbors",
+                     "voxel_outlier_mean_k", "voxel_outlier_stddev"):
             if getattr(flags, attr) is not None:
                 fail(f"--{attr.replace('_', '-')} needs --voxel-topic TOPIC")
         return None
@@ -677,11 +696,14 @@ def voxel_options(flags, error=None):
         kw["min_points"] = flags.voxel_min_points
     if flags.voxel_normals is not None:
         kw["normal_radius"] = flags.voxel_normals
-    names = {"leaf": "--voxel-leaf", "min_points": "--voxel-min-points", "normal_radius": "--voxel-normals"}
+    for attr, name in (("voxel_outlier_radius", "outlier_radius"), ("voxel_outlier_neighbors", "outlier_min_neighbors"),
+                       ("voxel_outlier_mean_k", "outlier_mean_k"), ("voxel_outlier_stddev", "outlier_stddev")):
+        if getattr(flags, attr) is not None:
+            kw[name] = getattr(flags, attr)
     try:
         return VoxelOptions(**kw)
     except ValueError as e:
-        fail(f"{names.get(str(e).split()[0], '--voxel-topic')}: {e}")
+        fail(f"{_VOXEL_FLAGS.get(str(e).split()[0], '--voxel-topic')}: {e}")
 
 
 def bev_view(engine, res: float, enabled):

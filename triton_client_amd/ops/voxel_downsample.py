@@ -43,7 +43,22 @@ Jacobi sweeps (``docs/precision.md`` has the rotation's operation order).  ``tca
 (``csrc/kernels/voxel_normals.hip``) gives its bytes on the device behind ``tca_voxel_downsample``,
 and :func:`normals_ref` is a float64 brute force with ``np.linalg.eigh``.
 
-Not here: averaging or carrying the other fields, ``filter_field_name`` limits and ``leaf_layout``,
+**Outliers** (``VoxelOptions.outlier_radius`` with ``outlier_min_neighbors`` and / or
+``outlier_mean_k``, ``outlier_stddev``; off by default; K36).  Between the two, what ``pcl_ros``'s
+``RadiusOutlierRemoval`` and ``StatisticalOutlierRemoval`` do behind a ``VoxelGrid``: lone voxels
+(rain, dust, ghosts) leave the cloud before the normals are taken, and the kept rows keep their
+order.  :func:`outliers_numpy` is the definition — the closed ball of the normals with the voxel
+itself left out, a voxel without a neighbour always gone, ``found >= N`` for the radius test, and for
+the statistical test the rounded mean of the rounded distances to the ``min(k, found)`` nearest
+against ``mean + stddev * sd`` of those means over the cloud (``docs/precision.md``) — and
+``tca_voxel_outliers`` (``csrc/kernels/voxel_outliers.hip``) gives its bytes on the device between
+the other two entries; :func:`outliers_ref` is a float64 brute force.  Three departures from PCL: the
+statistical test searches the ball only, where PCL's k-d tree search is unbounded (a voxel with fewer
+than ``k`` neighbours in the ball averages those it has); the query voxel is not its own neighbour
+(PCL's radius search counts it, and its SOR asks for ``k + 1`` to skip it); and the arithmetic is
+integer (distances in 2^-16 m, rounded), with both tests available at once.
+
+Not here: a radius that grows with range (DROR), filtering the unthinned cloud, averaging or carrying the other fields, ``filter_field_name`` limits and ``leaf_layout``,
 feeding the thinned cloud into the detectors or the other side outputs, tf, k-nearest search,
 viewpoints other than the origin, normals of the unthinned cloud.
 """
@@ -78,6 +93,9 @@ RADIUS_MIN, RADIUS_MAX = 0.02, 4.0  # of the normals' ball, metres
 RADIUS_LEAVES = 4  # the ball's radius is at most this many of the smallest leaf: at most 10^3 neighbours
 SWEEPS = 4  # cyclic Jacobi sweeps of the normals' eigen-solve (docs/precision.md)
 CELL_SLOT = 16  # bytes of a slot of the normals' cell table: key, count, start
+OUTLIER_NEIGHBORS = 1000  # the most outlier_min_neighbors: what a ball of RADIUS_LEAVES leaves can hold
+OUTLIER_K = 16  # the most outlier_mean_k: the squared distances a lane keeps in registers (32 VGPRs)
+OUTLIER_STDDEV = 10.0  # the most outlier_stddev
 # The launch's variants as they are run (``profiles/voxel_downsample/README.md`` has the measurements).
 DEFAULTS = {"wave": True, "lds": True, "saved": True}
 NORMALS_DEFAULTS = {"stage": False}  # (``profiles/voxel_normals/README.md``)
@@ -94,6 +112,21 @@ class VoxelOptions:
     leaf: object = 0.2  # one number, or (lx, ly, lz)
     min_points: int = 1
     normal_radius: float = 0.0  # metres; 0: no normals
+    outlier_radius: float = 0.0  # metres; 0: no outlier removal.  The ball of both tests below (K36)
+    outlier_min_neighbors: int = 0  # the radius test: kept from this many neighbours in the ball; 0: off
+    outlier_mean_k: int = 0  # the statistical test over the mean distance to this many nearest neighbours; 0: off
+    outlier_stddev: float = 1.0  # ... kept up to this many standard deviations above the cloud's mean
+
+    def _radius(self, name: str, sides) -> float:
+        r = _number(name, getattr(self, name))
+        if r != 0:
+            if not np.float32(RADIUS_MIN) <= np.float32(r) <= np.float32(RADIUS_MAX):
+                raise ValueError(f"{name} must be 0 (off) or lie within {RADIUS_MIN}..{RADIUS_MAX:g} m, got {r!r}")
+            if not max(self.l32) <= np.float32(r) <= np.float32(RADIUS_LEAVES) * min(self.l32):
+                raise ValueError(f"{name} must lie between the largest leaf and {RADIUS_LEAVES} times the smallest "
+                                 f"({max(sides):g}..{RADIUS_LEAVES * min(sides):g} m), got {r!r}")
+        object.__setattr__(self, name, r)
+        return r
 
     def __post_init__(self):
         v = self.leaf
@@ -108,14 +141,21 @@ class VoxelOptions:
                 raise ValueError(f"leaf must lie within {LEAF_MIN}..{LEAF_MAX:g} m on every axis, got {v!r}")
         object.__setattr__(self, "leaf", sides)
         C._count("min_points", self.min_points, 1, 2 ** 31 - 1)
-        r = _number("normal_radius", self.normal_radius)
-        if r != 0:
-            if not np.float32(RADIUS_MIN) <= np.float32(r) <= np.float32(RADIUS_MAX):
-                raise ValueError(f"normal_radius must be 0 (off) or lie within {RADIUS_MIN}..{RADIUS_MAX:g} m, got {r!r}")
-            if not max(self.l32) <= np.float32(r) <= np.float32(RADIUS_LEAVES) * min(self.l32):
-                raise ValueError(f"normal_radius must lie between the largest leaf and {RADIUS_LEAVES} times the smallest "
-                                 f"({max(sides):g}..{RADIUS_LEAVES * min(sides):g} m), got {r!r}")
-        object.__setattr__(self, "normal_radius", r)
+        self._radius("normal_radius", sides)
+        r = self._radius("outlier_radius", sides)
+        try:
+            n = C._count("outlier_min_neighbors", self.outlier_min_neighbors, 0, OUTLIER_NEIGHBORS)
+            k = C._count("outlier_mean_k", self.outlier_mean_k, 0, OUTLIER_K)
+        except ValueError as e:
+            raise ValueError(f"{e} (0: off)") from None
+        a = _number("outlier_stddev", self.outlier_stddev)
+        if not 0 <= a <= OUTLIER_STDDEV:
+            raise ValueError(f"outlier_stddev must lie within 0..{OUTLIER_STDDEV:g}, got {a!r}")
+        object.__setattr__(self, "outlier_stddev", a)
+        if r == 0 and (n or k):
+            raise ValueError(f"{'outlier_min_neighbors' if n else 'outlier_mean_k'} needs outlier_radius, the ball it searches")
+        if r != 0 and not (n or k):
+            raise ValueError("outlier_radius needs a test: outlier_min_neighbors or outlier_mean_k")
 
     @property
     def normals(self) -> bool:
@@ -125,6 +165,15 @@ class VoxelOptions:
     def radius_q(self) -> int:
         """The ball's radius in units of 2^-16 m."""
         return int(np.rint(np.float32(self.normal_radius) * np.float32(QC)))
+
+    @property
+    def outliers(self) -> bool:
+        return self.outlier_radius > 0
+
+    @property
+    def outlier_radius_q(self) -> int:
+        """The outlier tests' radius in units of 2^-16 m."""
+        return int(np.rint(np.float32(self.outlier_radius) * np.float32(QC)))
 
     @property
     def l32(self) -> Tuple[np.float32, np.float32, np.float32]:
@@ -361,6 +410,92 @@ def normals_ref(rows, opts: VoxelOptions, g: float = 0.05):
     return out, m, odd, flat
 
 
+# ---------------------------------------------------------------------------- outliers
+def outlier_scores_numpy(rows, opts: VoxelOptions) -> Tuple[np.ndarray, np.ndarray, float]:
+    """The integer half of the outliers' definition → ``(found int64 [K], mean int64 [K], thr)``: per
+    voxel the neighbours of its closed ball (itself excluded) and, with ``outlier_mean_k``, the rounded
+    mean of the rounded distances to the ``min(k, found)`` nearest in units of 2^-16 m (0 without a
+    neighbour); ``thr`` the statistical test's float64 threshold in the same units, ``inf`` where the
+    test is off or fewer than two voxels have a neighbour."""
+    c = _columns(rows)[:, :3]
+    K, k = len(c), opts.outlier_mean_k
+    q = np.rint(c * np.float32(QC)).astype(np.int64)
+    R = opts.outlier_radius_q
+    a, b = _pairs(q, R)
+    d = q[b] - q[a]
+    d2 = (d * d).sum(1)
+    near = (d2 <= R * R) & (a != b)
+    a, d2 = a[near], d2[near]
+    found = np.bincount(a, minlength=K).astype(np.int64)
+    mean, thr = np.zeros(K, np.int64), math.inf
+    if not k:
+        return found, mean, thr
+    order = np.lexsort((d2, a))  # by voxel, its squared distances ascending: only the values of the first k are used
+    a, d2 = a[order], d2[order]
+    first = np.arange(len(a)) - (np.cumsum(found) - found)[a] < k  # the rank inside the voxel's run
+    e = np.rint(np.sqrt(d2[first].astype(np.float64))).astype(np.int64)  # D^2 < 2^37: exact, the root correctly rounded
+    total = np.bincount(a[first], e.astype(np.float64), K)  # (exact: at most 16 * 2^18)
+    has = found >= 1
+    mean[has] = np.rint(total[has] / np.minimum(k, found[has]).astype(np.float64)).astype(np.int64)
+    n = int(has.sum())
+    if n >= 2:
+        s1, s2, fn = np.float64(int(mean[has].sum())), np.float64(int((mean[has] * mean[has]).sum())), np.float64(n)
+        mu = s1 / fn
+        var = (s2 - s1 * s1 / fn) / (fn - np.float64(1))  # PCL's sample variance
+        thr = float(mu + np.float64(opts.outlier_stddev) * np.sqrt(max(var, np.float64(0))))
+    return found, mean, thr
+
+
+def outliers_numpy(rows, opts: VoxelOptions) -> np.ndarray:
+    """The outliers' definition → the keep mask ``bool [K]`` of one cloud's rows ``[K, >=3]``: a voxel
+    without a neighbour goes; the radius test keeps ``found >= outlier_min_neighbors``, the statistical
+    test ``float64(mean) <= thr``, and with both on a voxel has to pass both."""
+    if not len(_columns(rows)):
+        return np.zeros(0, bool)
+    found, mean, thr = outlier_scores_numpy(rows, opts)
+    keep = found >= max(opts.outlier_min_neighbors, 1)
+    return keep & (mean.astype(np.float64) <= thr) if opts.outlier_mean_k else keep
+
+
+# what float64 may legitimately decide differently: a mean within this many metres of the threshold — four times the
+# worst |mean - mean_ref| + |thr - thr_ref| measured on the test scenes (docs/precision.md)
+OUTLIER_MARGIN = 4 * 2.31e-5
+
+
+def outlier_scores_ref(rows, opts: VoxelOptions):
+    """Float64 brute force with nothing of the definition's code → ``(found int64 [K], mean float64 [K],
+    thr, band bool [K])`` in metres: pairwise distances on ``float64(rows)`` against
+    ``float64(float32(r))``, ``np.partition`` for the nearest, ``np.std(ddof=1)``; ``band``: a pair of the
+    voxel lies within 2^-14 m of the radius."""
+    p = np.asarray(rows, np.float32)
+    p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 3)[:, :3].astype(np.float64)
+    r, k, K = float(np.float32(opts.outlier_radius)), opts.outlier_mean_k, len(p)
+    found, mean, band = np.zeros(K, np.int64), np.zeros(K), np.zeros(K, bool)
+    for a in range(K):
+        dist = np.delete(np.sqrt(((p - p[a]) ** 2).sum(1)), a)
+        band[a] = (np.abs(dist - r) <= 2.0 ** -14).any()
+        nb = dist[dist <= r]
+        found[a] = len(nb)
+        if k and len(nb):
+            f = min(k, len(nb))
+            mean[a] = np.partition(nb, f - 1)[:f].mean()
+    has = found >= 1
+    thr = float(mean[has].mean() + opts.outlier_stddev * np.std(mean[has], ddof=1)) if k and has.sum() >= 2 else math.inf
+    return found, mean, thr, band
+
+
+def outliers_ref(rows, opts: VoxelOptions, margin: float = OUTLIER_MARGIN) -> Tuple[np.ndarray, np.ndarray]:
+    """→ ``(keep bool [K], odd bool [K])`` of :func:`outlier_scores_ref`; ``odd``: the voxel's ball may
+    hold another set after the ``rint`` of its coordinates (``band``), or its mean lies within ``margin``
+    of the threshold."""
+    found, mean, thr, band = outlier_scores_ref(rows, opts)
+    keep = found >= max(opts.outlier_min_neighbors, 1)
+    if opts.outlier_mean_k:
+        keep &= mean <= thr
+        band = band | ((found >= 1) & (np.abs(mean - thr) <= margin))
+    return keep, band
+
+
 # ---------------------------------------------------------------------------- messages
 def downsample_message(cloud, rows: np.ndarray) -> msgs.PointCloud2:
     """The rows as an unorganised, little-endian ``PointCloud2`` with the cloud's header.  Rows of
@@ -382,8 +517,11 @@ def downsample_message(cloud, rows: np.ndarray) -> msgs.PointCloud2:
 
 
 def downsample_cloud_numpy(cloud, opts: VoxelOptions, lay: Optional[CloudLayout] = None) -> np.ndarray:
-    """One cloud through the definition → its rows, ``[K, 8]`` with normals on."""
+    """One cloud through the definition → its rows, ``[K, 8]`` with normals on; with the outlier filter
+    on the kept rows alone, and the normals of those."""
     rows = downsample_numpy(cloud_xyzi(cloud, lay), opts)
+    if opts.outliers:
+        rows = rows[outliers_numpy(rows, opts)]
     return np.concatenate([rows, normals_numpy(rows, opts)], 1) if opts.normals else rows
 
 
@@ -433,6 +571,12 @@ class VoxelCall:
     slots: Tuple[int, ...]
     opts: VoxelOptions
     normals: Optional[torch.Tensor] = None  # uint8, with normals on: 16 bytes per record at the record's index
+    kept: Optional[torch.Tensor] = None  # uint8, with the outlier filter on: the kept records, laid out like ``out``'s
+
+    @property
+    def records(self) -> torch.Tensor:
+        """The buffer that holds the published records: ``kept`` behind the outlier filter, else ``out``."""
+        return self.out if self.kept is None else self.kept
 
     @property
     def table_bytes(self) -> int:
@@ -461,8 +605,9 @@ class VoxelCall:
 
 def launch(c: VoxelCall, stream=None, wave: Optional[bool] = None, lds: Optional[bool] = None,
            saved: Optional[bool] = None, stage: Optional[bool] = None) -> None:
-    """The launch alone (five kernels on ``stream``, and with normals on the five of
-    ``tca_voxel_normals`` behind them): no allocation, no copy, no sync.  ``wave``:
+    """The launch alone (five kernels on ``stream``, with the outlier filter on the eight of
+    ``tca_voxel_outliers`` behind them and with normals on the five of ``tca_voxel_normals`` behind
+    those): no allocation, no copy, no sync.  ``wave``:
     runs of equal voxels of a wave are reduced with shuffles first; ``lds``: a workgroup gathers its
     span of points in a table in LDS; ``saved``: the scatter reads the slot the count pass kept
     instead of probing the table again.  None: :data:`DEFAULTS`.  ``stage``: the normals' fit stages
@@ -477,18 +622,33 @@ def launch(c: VoxelCall, stream=None, wave: Optional[bool] = None, lds: Optional
                  int(r.min_points), 1 if wave else 0, 1 if lds else 0, 1 if saved else 0, p(c.table), c.table_bytes,
                  p(c.memo), c.memo_bytes, p(c.blocks), c.blocks_bytes, p(c.out), c.rows_bytes, p(c.counts),
                  _native.stream_ptr(stream))
+    if r.outliers:
+        launch_outliers(c, stream)
     if r.normals:
         launch_normals(c, stream, stage)
 
 
+def launch_outliers(c: VoxelCall, stream=None) -> None:
+    """``tca_voxel_outliers`` alone, behind a ``tca_voxel_downsample`` of the same call on ``stream``: it
+    reads the records and the counts on the device, writes the kept records to ``c.kept`` and the
+    survivors of every cloud over its count; the leaf table, the memo and the block counts, all dead
+    after the scatter, are its workspace."""
+    p, r = _native.ptr, c.opts
+    ns, slots = np.asarray(c.ns, np.int32), np.asarray(c.slots, np.int32)
+    _native.call("tca_voxel_outliers", p(c.out), c.rows_bytes, p(c.counts), ns.ctypes.data, slots.ctypes.data, c.batch,
+                 r.outlier_radius_q, int(r.outlier_min_neighbors), int(r.outlier_mean_k), float(r.outlier_stddev),
+                 p(c.table), c.table_bytes, p(c.memo), c.memo_bytes, p(c.blocks), c.blocks_bytes, p(c.kept),
+                 c.rows_bytes, _native.stream_ptr(stream))
+
+
 def launch_normals(c: VoxelCall, stream=None, stage: Optional[bool] = None) -> None:
-    """``tca_voxel_normals`` alone, behind a ``tca_voxel_downsample`` of the same call on ``stream``: it
-    reads the records and the counts on the device, and the leaf table, dead after the scatter, is
-    the cell lists' workspace."""
+    """``tca_voxel_normals`` alone, behind a ``tca_voxel_downsample`` (and the outlier filter, when on)
+    of the same call on ``stream``: it reads the records and the counts on the device, and the leaf
+    table, dead after the scatter, is the cell lists' workspace."""
     stage = NORMALS_DEFAULTS["stage"] if stage is None else stage
     p = _native.ptr
     ns, slots = np.asarray(c.ns, np.int32), np.asarray(c.slots, np.int32)
-    _native.call("tca_voxel_normals", p(c.out), c.rows_bytes, p(c.counts), ns.ctypes.data, slots.ctypes.data,
+    _native.call("tca_voxel_normals", p(c.records), c.rows_bytes, p(c.counts), ns.ctypes.data, slots.ctypes.data,
                  c.batch, c.opts.radius_q, 1 if stage else 0, p(c.table), c.table_bytes, p(c.normals), c.rows_bytes,
                  _native.stream_ptr(stream))
 
@@ -499,10 +659,14 @@ def layout_device_ok(lay: CloudLayout) -> bool:
     return fields_f32(lay, (0, 1, 2, 3) if lay.offsets[3] >= 0 else (0, 1, 2))
 
 
-def rows_of(host: np.ndarray, c: VoxelCall, normals: Optional[np.ndarray] = None) -> List[np.ndarray]:
+def rows_of(host: np.ndarray, c: VoxelCall, normals: Optional[np.ndarray] = None,
+            kept: Optional[np.ndarray] = None) -> List[np.ndarray]:
     """Per cloud its rows ``float32 [K, 4]`` (copies) of a launch's output bytes (``out_bytes`` of them);
-    with the bytes of its normals (``rows_bytes`` of them), ``[K, 8]``."""
+    with the bytes of its normals (``rows_bytes`` of them), ``[K, 8]``.  ``kept``: the bytes of the
+    outlier filter's records (``rows_bytes`` of them), read in place of the output's; the counts are the
+    output's either way."""
     counts = host[c.rows_bytes:c.out_bytes].view("<i4")
+    host = host if kept is None else kept
     res, at = [], 0
     for b, n in enumerate(c.ns):
         k = int(counts[b])
@@ -554,13 +718,15 @@ class VoxelDownsampler(CloudStager):
         c.out = self._device_buf("voxel_out", c.out_bytes)
         if opts.normals:
             c.normals = self._device_buf("voxel_normals", c.rows_bytes)
+        if opts.outliers:
+            c.kept = self._device_buf("voxel_kept", c.rows_bytes)
         return c
 
     launch = staticmethod(launch)
 
     def _fetch_counted(self, c: VoxelCall, st) -> Tuple[np.ndarray, Optional[np.ndarray]]:
-        """The counts, a synchronize, then only the used records of every cloud's slot, and with
-        normals on the same parts of the normals → the host bytes, laid out like the output, and the
+        """The counts (behind the outlier filter the survivors), a synchronize, then only the used
+        records of every cloud's slot, and with normals on the same parts of the normals → the host bytes, laid out like the output, and the
         normals' (None when off)."""
         on = c.normals is not None
         pin = self._pinned("_pin_out", _align(c.out_bytes) + c.rows_bytes if on else c.out_bytes)
@@ -574,7 +740,7 @@ class VoxelDownsampler(CloudStager):
             for b, n in enumerate(c.ns):
                 lo, hi = RECORD * at, RECORD * (at + int(counts[b]))
                 if hi > lo:
-                    pin[lo:hi].copy_(c.out[lo:hi], non_blocking=True)
+                    pin[lo:hi].copy_(c.records[lo:hi], non_blocking=True)
                     if on:
                         side[lo:hi].copy_(c.normals[lo:hi], non_blocking=True)
                 at += n
