@@ -138,6 +138,8 @@ def main():
     ap.add_argument("--grid", action="store_true",
                     help="LiDAR side: also publish every cloud as a ray-cast OccupancyGrid, the sensor height the synthetic "
                          "sweep's and the other options at their defaults (RosInference3D grid_topic)")
+    ap.add_argument("--grid-inflation", type=float, default=0.0, metavar="M",
+                    help="--grid: inflate the grid's obstacles by M metres (GridOptions inflation_radius; default 0: off)")
     ap.add_argument("--voxel", action="store_true",
                     help="LiDAR side: also publish every cloud thinned on a voxel grid, the options at their defaults "
                          "(RosInference3D voxel_topic)")
@@ -293,6 +295,8 @@ def main():
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.clusters else {}),
                              **({"grid_topic": "/pc_grid",
                                  "ground_options": {"sensor_height": spec.sensor_height}} if a.grid else {}),
+                             **({"grid_options": {"inflation_radius": a.grid_inflation}}
+                                if a.grid and a.grid_inflation else {}),
                              **({"voxel_topic": "/pc_voxels"} if a.voxel else {}),
                              **({"voxel_options": vopts} if a.voxel and vopts else {}))
         if a.clusters:
@@ -425,7 +429,7 @@ def main():
             out["lidar"]["grid_mapper"] = kind
             mean = (np.sum(grids, 0) / max(1, len(grids))).round().astype(int).tolist() if grids else [0, 0, 0]
             out["lidar"]["grid"] = {"messages": len(grids), "occupied_cells": mean[0], "free_cells": mean[1],
-                                    "unknown_cells": mean[2]}
+                                    "unknown_cells": mean[2], "inflation_cells": o.inflation_cells}
         if a.voxel:
             from triton_client_amd.inference.engines import Detector3D
             from triton_client_amd.ops.voxel_downsample import device_enabled

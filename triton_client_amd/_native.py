@@ -112,6 +112,10 @@ _KERNEL_SIGS = {
     # keys), aggregate (1; 0: one atomic per point), stage_keys (0; 1: near / far in LDS in the cell pass), cells, its
     # bytes, keys, its bytes, out, its bytes, stream (csrc/kernels/occupancy_grid.hip)
     "tca_occupancy_grid": [P, L, P, P, P, I, I, I, I, I, I, P, I, F, F, F, I, I, I, F, I, I, I, P, L, P, L, P, L, P],
+    # tca_occupancy_grid's planes, their bytes, B, W, H, the radius in cells (1..64), the cost table (device uint8
+    # [R * R + 1]), its bytes, inflate_unknown, skip_empty (1; 0: tiles with no obstacle near them are walked too), out
+    # (another buffer, the planes' layout), its bytes, stream (csrc/kernels/grid_inflate.hip)
+    "tca_grid_inflate": [P, L, I, I, I, I, P, L, I, I, P, L, P],
     # data, data bytes, frame_off, frame_n, ns (HOST int32 [B]), slots (HOST int32 [B]: every cloud's table size), B,
     # point_step, off x/y/z/intensity (-1: none), float32 leaf x/y/z, min_points, wave (1; 0: no reduction over a
     # wave's runs), lds (1: a workgroup table in LDS), saved (1; 0: the scatter probes again), table, its bytes, memo,

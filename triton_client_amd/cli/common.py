@@ -573,7 +573,9 @@ def cluster_fit_options(flags, error=None):
 
 
 _GRID_FLAGS = (("grid_cell", "cell"), ("grid_x_range", "x_range"), ("grid_y_range", "y_range"),
-               ("grid_sectors", "sectors"), ("grid_min_points", "min_points"), ("grid_clear_radius", "clear_radius"))
+               ("grid_sectors", "sectors"), ("grid_min_points", "min_points"), ("grid_clear_radius", "clear_radius"),
+               ("grid_inflation_radius", "inflation_radius"), ("grid_inscribed_radius", "inscribed_radius"),
+               ("grid_cost_scaling", "cost_scaling"), ("grid_inflate_unknown", "inflate_unknown"))
 
 
 def add_grid_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
@@ -593,6 +595,17 @@ def add_grid_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
     p.add_argument("--grid-clear-radius", type=float, default=None, metavar="M",
                    help="cells whose centre is nearer to the sensor than this are free: the vehicle's own footprint "
                         "(default 0)")
+    p.add_argument("--grid-inflation-radius", type=float, default=None, metavar="M",
+                   help="inflate the grid's obstacles by this many metres with costmap_2d's costs 1..99 (default 0: "
+                        "off; at most 64 cells of --grid-cell)")
+    p.add_argument("--grid-inscribed-radius", type=float, default=None, metavar="M",
+                   help="cells this near to an obstacle cost 99: the robot's inscribed radius (default 0; at most "
+                        "--grid-inflation-radius, which it needs)")
+    p.add_argument("--grid-cost-scaling", type=float, default=None, metavar="K",
+                   help="how fast the cost falls with the distance: costmap_2d's cost_scaling_factor (default 10; "
+                        "0..100; needs --grid-inflation-radius)")
+    p.add_argument("--grid-inflate-unknown", action="store_true", default=None,
+                   help="unknown cells take every cost above 0, not only 99 (needs --grid-inflation-radius)")
     p.add_argument("--grid-frame-id", default=None, metavar="FRAME",
                    help="frame_id of the grid messages (default: the cloud's)")
 

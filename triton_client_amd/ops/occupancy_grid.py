@@ -32,8 +32,21 @@ that holds a ground return is free whatever stands in front of it), or
 ``key(r_c) < min(near[s_c], far[s_c])``; **-1** otherwise — the shadow behind the first obstacle
 and every direction without a return.  Nothing depends on the order of the points.
 
-Not here: tf and ``target_frame``, accumulation over time (log-odds), inflation and costs other
-than -1 / 0 / 100, and ``map_server`` files.
+**Inflation** (K37, ``inflation_radius > 0``; off by default) is ``costmap_2d``'s inflation layer on
+that plane, so that a planner can take the topic as it is.  ``Rc = ceil(inflation_radius / cell)``
+cells (``cellDistance``, 1..64); :func:`cost_table` holds, per squared distance ``d2`` in cells, the
+byte ROS publishes for ``InflationLayer::computeCost`` (100 on the obstacle, 99 within
+``inscribed_radius``, then ``252 * exp(-cost_scaling * (dist - inscribed_radius))`` through
+``Costmap2DPublisher``'s translation to 1..98, 0 beyond).  It is made on the host in float64 and is an
+input of the definition and of the device alike.  :func:`inflate_numpy` is the definition: per cell
+``d2`` is the smallest ``dx*dx + dy*dy`` to a cell of value 100 of the same plane (outside the plane
+nothing is occupied), ``c = table[d2]`` for ``d2 <= Rc*Rc`` and 0 beyond; 100 stays, 0 becomes ``c``,
+-1 becomes ``c`` where ``c >= 99`` (with ``inflate_unknown``: where ``c > 0``) and stays -1
+otherwise — the layer's ``NO_INFORMATION`` rule.  Integers only: the kernel ``tca_grid_inflate``
+(``csrc/kernels/grid_inflate.hip``) and the brute force :func:`inflate_ref` give equal bytes.
+
+Not here: tf and ``target_frame``, accumulation over time (log-odds), footprints other than a circle,
+``inflate_around_unknown``, inflation in the ring engines, and ``map_server`` files.
 """
 from __future__ import annotations
 
@@ -56,6 +69,7 @@ from .range2d import U, _xyz
 MAX_FRAMES = 64  # clouds per launch
 MAX_SECTORS = 4096
 MAX_PLANE = 2 ** 24  # cells of one launch
+MAX_INFLATION_CELLS = 64  # K37: the halo of a tile
 OCCUPIED, FREE, UNKNOWN = 100, 0, -1
 NO_KEY = 0xFFFFFFFF  # near[] of a sector without an obstacle record
 GROUND_BIT = 0x80000000  # of a cell word; the obstacle count is below it
@@ -76,6 +90,10 @@ class GridOptions:
     sectors: int = 720
     min_points: int = 1
     clear_radius: float = 0.0
+    inflation_radius: float = 0.0  # metres; 0: off (costmap_2d's inflation_radius)
+    inscribed_radius: float = 0.0  # metres: cells this near to an obstacle cost 99
+    cost_scaling: float = 10.0  # costmap_2d's cost_scaling_factor
+    inflate_unknown: bool = False
 
     z_range = (-C.LIMIT, C.LIMIT)  # (not a field) what ``cluster.cells_numpy`` reads
 
@@ -100,6 +118,24 @@ class GridOptions:
         C._count("min_points", self.min_points, 1, 2 ** 31 - 1)
         if not _number("clear_radius", self.clear_radius) >= 0:
             raise ValueError(f"clear_radius must be >= 0, got {self.clear_radius!r}")
+        radius = _number("inflation_radius", self.inflation_radius)
+        inscribed = _number("inscribed_radius", self.inscribed_radius)
+        scaling = _number("cost_scaling", self.cost_scaling)
+        if not isinstance(self.inflate_unknown, (bool, np.bool_)):
+            raise ValueError(f"inflate_unknown must be a bool, got {self.inflate_unknown!r}")
+        if not radius >= 0:
+            raise ValueError(f"inflation_radius must be >= 0, got {radius!r}")
+        if not 0 <= scaling <= 100:
+            raise ValueError(f"cost_scaling must be within 0..100, got {scaling!r}")
+        if radius == 0:
+            for name, off in (("inscribed_radius", 0.0), ("cost_scaling", 10.0), ("inflate_unknown", False)):
+                if getattr(self, name) != off:
+                    raise ValueError(f"{name} needs inflation_radius")
+        elif not 1 <= self.inflation_cells <= MAX_INFLATION_CELLS:
+            raise ValueError(f"inflation_radius gives {self.inflation_cells} cells of {cell!r} m, want "
+                             f"1..{MAX_INFLATION_CELLS}")
+        if not 0 <= inscribed <= radius:
+            raise ValueError(f"inscribed_radius must be within 0..inflation_radius, got {inscribed!r}")
 
     _side = C.ClusterOptions._side
 
@@ -114,6 +150,15 @@ class GridOptions:
     @property
     def c32(self) -> np.float32:
         return np.float32(self.cell)
+
+    @property
+    def inflation(self) -> bool:
+        return self.inflation_radius > 0
+
+    @property
+    def inflation_cells(self) -> int:
+        """``Rc``: ``costmap_2d``'s ``cellDistance`` of the radius."""
+        return int(math.ceil(float(np.float32(self.inflation_radius)) / float(self.c32)))
 
     @property
     def stride(self) -> int:
@@ -176,7 +221,8 @@ def grid_cloud_numpy(cloud, opts: GridOptions, ground_opts: Optional[G.GroundOpt
                      lay: Optional[CloudLayout] = None) -> np.ndarray:
     """One cloud through the definitions: ``split_numpy`` (``ground_opts``: its options, the
     defaults without), then :func:`grid_numpy` on the two row sets."""
-    return grid_numpy(*split_rows(cloud_xyzi(cloud, lay), ground_opts), opts)
+    plane = grid_numpy(*split_rows(cloud_xyzi(cloud, lay), ground_opts), opts)
+    return inflate_numpy(plane, opts) if opts.inflation else plane
 
 
 def grid_ref(obstacles, ground, opts: GridOptions):
@@ -259,6 +305,78 @@ def grid_ref(obstacles, ground, opts: GridOptions):
     return np.where(ocnt >= opts.min_points, OCCUPIED, np.where(free, FREE, UNKNOWN)).astype(np.int8), flat
 
 
+# --------------------------------------------------------------------------- inflation
+NO_ROW = 255  # the row distance of a cell with no occupied cell of its row within Rc: 255 * 255 > 64 * 64
+
+
+def cost_table(opts: GridOptions) -> np.ndarray:
+    """The published cost by squared distance in cells → ``int8 [Rc * Rc + 1]``, in float64 on the
+    host: ``InflationLayer::computeCost`` (truncated as its ``unsigned char`` cast does), then
+    ``Costmap2DPublisher``'s translation table (254 → 100, 253 → 99, 1..252 → 1..98)."""
+    Rc, c = opts.inflation_cells, float(opts.c32)
+    inscribed, scaling = float(np.float32(opts.inscribed_radius)), float(np.float32(opts.cost_scaling))
+    lut = np.zeros(Rc * Rc + 1, np.int8)
+    lut[0] = OCCUPIED
+    for d2 in range(1, Rc * Rc + 1):
+        dist = math.sqrt(float(d2)) * c
+        if dist <= inscribed:
+            lut[d2] = 99
+            continue
+        cost = int(252 * math.exp(-scaling * (dist - inscribed)))
+        lut[d2] = 0 if cost == 0 else 1 + (97 * (cost - 1)) // 251
+    return lut
+
+
+def _inflated(p: np.ndarray, c: np.ndarray, opts: GridOptions) -> np.ndarray:
+    """The value rule: ``p`` the plane's own values, ``c`` the cost of every cell."""
+    take = (p == FREE) | ((p == UNKNOWN) & ((c > 0) if opts.inflate_unknown else (c >= 99)))
+    return np.where(take, c, p).astype(np.int8)
+
+
+def inflate_numpy(plane, opts: GridOptions) -> np.ndarray:
+    """The definition of K37 → ``int8 [H * W]``: a separable two-pass integer minimum.  ``g`` is the
+    distance along the row to the nearest occupied cell within ``Rc`` (``NO_ROW`` without one), then
+    ``d2 = min over dy in -Rc..Rc of dy*dy + g*g`` of the row ``dy`` away; rows and columns outside
+    the plane hold nothing."""
+    W, H, Rc = opts.W, opts.H, opts.inflation_cells
+    p = np.ascontiguousarray(plane, np.int8).reshape(H, W)
+    occ = np.zeros((H, W + 2 * Rc), bool)
+    occ[:, Rc:Rc + W] = p == OCCUPIED
+    g = np.full((H + 2 * Rc, W), NO_ROW, np.int64)
+    for dx in range(-Rc, Rc + 1):
+        np.minimum(g[Rc:Rc + H], np.where(occ[:, Rc + dx:Rc + dx + W], abs(dx), NO_ROW), out=g[Rc:Rc + H])
+    g2 = g * g
+    d2 = g2[Rc:Rc + H].copy()
+    for dy in range(1, Rc + 1):
+        np.minimum(d2, dy * dy + np.minimum(g2[Rc - dy:Rc - dy + H], g2[Rc + dy:Rc + dy + H]), out=d2)
+    c = np.where(d2 <= Rc * Rc, cost_table(opts)[np.minimum(d2, Rc * Rc)], 0)
+    return _inflated(p, c, opts).reshape(-1)
+
+
+def inflate_ref(plane, opts: GridOptions) -> np.ndarray:
+    """A brute force with none of the definition's code: the offsets of the disc in ascending
+    ``d2``, each ORing the shifted occupied mask into the plane of the ``d2`` a cell was first
+    reached at; then the value rule, cell by cell.  Integers: equal to the definition, no band."""
+    W, H, Rc = opts.W, opts.H, opts.inflation_cells
+    lut = cost_table(opts)
+    p = np.asarray(plane).reshape(H, W)
+    first = np.full((H, W), -1, np.int64)
+    disc = sorted((dx * dx + dy * dy, dx, dy) for dx in range(-Rc, Rc + 1) for dy in range(-Rc, Rc + 1)
+                  if dx * dx + dy * dy <= Rc * Rc)
+    for d2, dx, dy in disc:  # cell (y, x) is reached from an occupied (y + dy, x + dx)
+        ys, xs = slice(max(0, -dy), min(H, H - dy)), slice(max(0, -dx), min(W, W - dx))
+        src = p[max(0, dy):min(H, H + dy), max(0, dx):min(W, W + dx)] == 100
+        first[ys, xs] = np.where(src & (first[ys, xs] < 0), d2, first[ys, xs])
+    out = np.empty((H, W), np.int8)
+    for y in range(H):
+        for x in range(W):
+            v, c = int(p[y, x]), int(lut[first[y, x]]) if first[y, x] >= 0 else 0
+            if v == 0 or (v == -1 and (c >= 99 or (opts.inflate_unknown and c >= 1))):
+                v = c
+            out[y, x] = v
+    return out.reshape(-1)
+
+
 # ---------------------------------------------------------------------------- messages
 def grid_message(cloud, data: np.ndarray, opts: GridOptions, frame_id: str = "") -> msgs.OccupancyGrid:
     """The plane as a ``nav_msgs/OccupancyGrid`` with the cloud's stamp and seq, in frame
@@ -287,6 +405,8 @@ class GridCall:
     out: torch.Tensor  # uint8: the planes, ``stride`` bytes apart
     batch: int
     opts: GridOptions
+    inflated: Optional[torch.Tensor] = None  # uint8: K37's planes, laid out as ``out`` (with ``opts.inflation``)
+    lut: Optional[torch.Tensor] = None  # uint8 view of int8 [Rc * Rc + 1]: the cost table
 
     @property
     def cells_bytes(self) -> int:
@@ -302,11 +422,13 @@ class GridCall:
         return (self.batch - 1) * self.opts.stride + self.opts.W * self.opts.H
 
 
-def launch(c: GridCall, stream=None, privatise: bool = True, aggregate: bool = True, stage_keys: bool = False) -> None:
+def launch(c: GridCall, stream=None, privatise: bool = True, aggregate: bool = True, stage_keys: bool = False,
+           skip_empty: bool = True) -> None:
     """The launch alone (the ground split's six kernels, then the reset, the points pass and the
-    cell pass on ``stream``): no allocation, no copy, no sync.  ``privatise`` False: no LDS sector
-    keys; ``aggregate`` False: one atomic per point; ``stage_keys``: the cell pass stages ``near``
-    and ``far`` in LDS (measurements)."""
+    cell pass on ``stream``, and with ``opts.inflation`` K37 behind them): no allocation, no copy,
+    no sync.  ``privatise`` False: no LDS sector keys; ``aggregate`` False: one atomic per point;
+    ``stage_keys``: the cell pass stages ``near`` and ``far`` in LDS; ``skip_empty`` False: K37 walks
+    the tiles with no obstacle near them too (measurements)."""
     p = _native.ptr
     g, r = c.ground, c.opts
     G.launch(g, G.WANT_OBSTACLES | G.WANT_GROUND, stream)
@@ -316,6 +438,17 @@ def launch(c: GridCall, stream=None, privatise: bool = True, aggregate: bool = T
                  float(np.float32(r.x_range[0])), float(np.float32(r.y_range[0])), float(r.c32), r.W, r.H,
                  int(r.min_points), float(np.float32(r.clear_radius)), 1 if privatise else 0, 1 if aggregate else 0,
                  1 if stage_keys else 0, p(c.cells), c.cells_bytes, p(c.keys), c.keys_bytes, p(c.out), c.out_bytes,
+                 _native.stream_ptr(stream))
+    if r.inflation:
+        inflate(c, stream, skip_empty)
+
+
+def inflate(c: GridCall, stream=None, skip_empty: bool = True) -> None:
+    """K37 alone: ``c.out``'s planes → ``c.inflated``."""
+    p, r = _native.ptr, c.opts
+    Rc = r.inflation_cells
+    _native.call("tca_grid_inflate", p(c.out), c.out_bytes, c.batch, r.W, r.H, Rc, p(c.lut), Rc * Rc + 1,
+                 1 if r.inflate_unknown else 0, 1 if skip_empty else 0, p(c.inflated), c.out_bytes,
                  _native.stream_ptr(stream))
 
 
@@ -334,7 +467,8 @@ class GridMapper(CloudStager):
     """Turns clouds into occupancy grids: on a GPU a :class:`~triton_client_amd.ops.ground.GroundSplitter`
     of its own on the same workspace stages the clouds, its launch runs first and
     ``tca_occupancy_grid`` reads the slab and the counts where they lie (no byte goes to the host
-    in between; one D2H of ``H * W`` bytes per cloud); on the CPU — and with ``TCA_DEVICE_GRID=0``
+    in between; one D2H of ``H * W`` bytes per cloud; with ``opts.inflation`` ``tca_grid_inflate``
+    runs behind it and its planes are the ones fetched); on the CPU — and with ``TCA_DEVICE_GRID=0``
     or ``TCA_DEVICE_GROUND=0`` — the definitions.  Clouds the kernels do not take (non-FLOAT32 or
     big-endian fields) run the definitions with one warning.  ``privatise``, ``aggregate``,
     ``stage_keys``: the launch's variants (measurements)."""
@@ -356,15 +490,23 @@ class GridMapper(CloudStager):
             raise ValueError(f"{B} clouds of {opts.W} x {opts.H} cells do not fit one call ({MAX_PLANE}): split the "
                              "batch")
         g = self.splitter.prepare(payloads, ns, layout, ground or G.GroundOptions(), stream, misalign)
-        pin = self._pinned("_pin_in", 4 * (S + 1))
+        costs = cost_table(opts).view(np.uint8) if opts.inflation else np.zeros(0, np.uint8)
+        at = _align(4 * (S + 1))  # the cost table's place in the pinned bytes, behind the edges
+        pin = self._pinned("_pin_in", at + len(costs) if opts.inflation else 4 * (S + 1))
         pin.numpy()[:4 * (S + 1)] = G.edge_table(opts).view(np.uint8)
+        pin.numpy()[at:at + len(costs)] = costs
         table = self._device_buf("grid_table", 4 * (S + 1))
+        lut = self._device_buf("grid_lut", len(costs)) if opts.inflation else None
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
             table[:4 * (S + 1)].copy_(pin[:4 * (S + 1)], non_blocking=True)
-        c = GridCall(ground=g, table=table, cells=None, keys=None, out=None, batch=B, opts=opts)
+            if lut is not None:
+                lut[:len(costs)].copy_(pin[at:at + len(costs)], non_blocking=True)
+        c = GridCall(ground=g, table=table, cells=None, keys=None, out=None, batch=B, opts=opts, lut=lut)
         c.cells = self._device_buf("grid_cells", c.cells_bytes)
         c.keys = self._device_buf("grid_keys", c.keys_bytes)
         c.out = self._device_buf("grid_out", c.out_bytes)
+        if opts.inflation:
+            c.inflated = self._device_buf("grid_inflated", c.out_bytes)
         return c
 
     launch = staticmethod(launch)
@@ -375,7 +517,7 @@ class GridMapper(CloudStager):
             st = self._own_stream()
             c = self.prepare(payloads, ns, layout, opts, ground, st)
             launch(c, st, self.privatise, self.aggregate, self.stage_keys)
-            return planes_of(self._fetch(c.out, c.out_bytes, st), c.batch, opts)
+            return planes_of(self._fetch(c.inflated if opts.inflation else c.out, c.out_bytes, st), c.batch, opts)
 
     def _parts_for(self, opts: GridOptions, ground: Optional[G.GroundOptions]):
         """The cut of a layout's clouds into launches (:func:`most_clouds`, less than 2^31 staged bytes)."""
