@@ -118,6 +118,8 @@ def main():
                     help="LiDAR side: also publish every cloud as a 16UC1 depth Image of --depth-size pixels under a "
                          "fixed KITTI-like calibration rescaled to that size (RosInference3D depth_topic)")
     ap.add_argument("--depth-size", default="1280x720", metavar="WxH")
+    ap.add_argument("--depth-fill", type=int, default=0, metavar="K",
+                    help="with --depth: fill the image's holes (K38), the other radii at their defaults; 0: off")
     ap.add_argument("--scan", action="store_true",
                     help="LiDAR side: also publish every cloud as a LaserScan of --scan-bins rays over the full circle, "
                          "the other options at their defaults (RosInference3D scan_topic)")
@@ -174,6 +176,8 @@ def main():
     a = ap.parse_args()
     if a.depth and a.ranged:
         ap.error("--depth rescales the calibration that --ranged uses as it is: run them apart")
+    if a.depth_fill and not a.depth:
+        ap.error("--depth-fill needs --depth")
     if a.clusters_oriented and not a.clusters:
         ap.error("--clusters-oriented needs --clusters")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # self-launch (a child: nothing has touched the GPU)
@@ -388,6 +392,7 @@ def main():
             print(f"depth images: {kind}", file=sys.stderr)
             out["lidar"]["output"] += f" + depth Image {o.encoding} {o.width}x{o.height} ({kind})"
             out["lidar"]["depth_imager"] = kind
+            out["lidar"]["depth_fill"] = o.fill
             out["lidar"]["depth"] = {"messages": len(depth), "bytes_per_image": round(sum(depth) / max(1, len(depth)))}
         if a.scan:
             from triton_client_amd.inference.engines import Detector3D
@@ -518,7 +523,8 @@ def _depth_arguments(a):
     w, h = (int(v) for v in a.depth_size.lower().split("x"))
     cal = _kitti_like_calibration()
     P = np.diag([w / 1242.0, h / 375.0, 1.0]) @ cal.P
-    return {"depth_topic": "/pc_depth", "depth_options": DepthOptions(w, h), "calibration": Calibration(P, cal.T)}
+    return {"depth_topic": "/pc_depth", "depth_options": DepthOptions(w, h, fill=a.depth_fill),
+            "calibration": Calibration(P, cal.T)}
 
 
 def _scan_arguments(a):

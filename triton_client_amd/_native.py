@@ -88,6 +88,11 @@ _KERNEL_SIGS = {
     # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z, M (host), W, H, encoding (0: 16UC1,
     # 1: 32FC1), scale, min_depth, splat, plane, out, stream (csrc/kernels/depth_image.hip)
     "tca_depth_image": [P, L, P, P, I, I, I, I, I, I, P, I, I, I, F, F, I, P, P, P],
+    # tca_depth_image's key planes, their bytes, B, W, H, encoding, k (1..4), hole (0..7), large (0..15), median
+    # (0..2), fused (0: two launches through scratch; 1: one), skip_empty (1; 0: tiles without a key are walked too),
+    # scratch (another B * H * W uint32; may be null when fused), its bytes, out, its bytes, stream
+    # (csrc/kernels/depth_fill.hip)
+    "tca_depth_fill": [P, L, I, I, I, I, I, I, I, I, I, I, P, L, P, L, P],
     # data, data bytes, frame_off, frame_n, B, max_n, point_step, off x/y/z, edge table (device float[n + 1]), n,
     # min_height, max_height, range_min, range_max, empty bits, privatise (1; 0: no LDS bins, measurements), plane,
     # out, stream (csrc/kernels/laser_scan.hip)

@@ -260,7 +260,8 @@ def range_options(flags, error=None):
     return cal, opts
 
 
-_DEPTH_FLAGS = ("depth_size", "depth_encoding", "depth_scale", "depth_min", "depth_splat", "depth_frame_id")
+_DEPTH_FLAGS = ("depth_size", "depth_encoding", "depth_scale", "depth_min", "depth_splat", "depth_frame_id",
+                "depth_fill", "depth_fill_hole", "depth_fill_large", "depth_fill_median")
 
 
 def add_depth_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
@@ -279,6 +280,15 @@ def add_depth_flags(p: argparse.ArgumentParser, topic_help: str) -> None:
                    help="a point covers the (2R+1)^2 pixels around its own, 0..4 (default 1)")
     p.add_argument("--depth-frame-id", default=None, metavar="FRAME",
                    help="frame_id of the depth images (default: the cloud's)")
+    p.add_argument("--depth-fill", type=int, default=None, metavar="K",
+                   help="fill the image's holes (IP-Basic: dilate, close, fill, median); K, 1..4, is the half-width of "
+                        "the first dilation's diamond and of the closing (the paper uses 2; default 0: off)")
+    p.add_argument("--depth-fill-hole", type=int, default=None, metavar="H",
+                   help="with --depth-fill: half-width of the small-hole fill, 0..7 (default 3; 0 skips it)")
+    p.add_argument("--depth-fill-large", type=int, default=None, metavar="G",
+                   help="with --depth-fill: half-width of the large-hole fill, 0..15 (default 15; 0 skips it)")
+    p.add_argument("--depth-fill-median", type=int, default=None, metavar="M",
+                   help="with --depth-fill: half-width of the median, 0..2 (default 2; 0 skips it)")
 
 
 def depth_options(flags, error=None):
@@ -315,8 +325,14 @@ def depth_options(flags, error=None):
         fail(f"--depth-size: want WxH, e.g. 1280x720, got {flags.depth_size!r}")
     if out_dir and flags.depth_encoding == "32FC1":
         fail("--depth-out writes 16-bit PNGs: it needs --depth-encoding 16UC1")
+    if not flags.depth_fill:
+        for f in ("depth_fill_hole", "depth_fill_large", "depth_fill_median"):
+            if getattr(flags, f) is not None:
+                fail(f"--{f.replace('_', '-')} needs --depth-fill K")
     kw = {k: v for k, v in (("encoding", flags.depth_encoding), ("scale", flags.depth_scale),
-                            ("min_depth", flags.depth_min), ("splat", flags.depth_splat)) if v is not None}
+                            ("min_depth", flags.depth_min), ("splat", flags.depth_splat), ("fill", flags.depth_fill),
+                            ("fill_hole", flags.depth_fill_hole), ("fill_large", flags.depth_fill_large),
+                            ("fill_median", flags.depth_fill_median)) if v is not None}
     try:
         opts = DepthOptions(width=w, height=h, **kw)
         cal = cal if cal is not None else load_calibration(flags.calib)

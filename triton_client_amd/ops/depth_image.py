@@ -30,6 +30,26 @@ the per-point code sees.  :class:`DepthOptions`: ``width`` ``W`` and ``height`` 
 no point covers holds 0 in ``16UC1`` and the quiet NaN with bits ``0x7FC00000`` in ``32FC1``.  The
 output is ``[H, W]`` ``<u2`` or ``<f4``.  The minimum is commutative: nothing depends on the
 order of the points.
+
+**Hole filling (K38)**, ``fill = k > 0``: IP-Basic's fast pipeline (Ku, Harakeh, Waslander 2018, "In
+Defense of Classical Image Processing: Fast Depth Completion on the CPU") on the uint32 key plane,
+before it becomes the image.  :func:`fill_numpy` is the definition, :func:`fill_ref` a brute force
+that shares nothing with it, and ``tca_depth_fill`` (``csrc/kernels/depth_fill.hip``) gives the same
+bytes on the device.  ``E = 0xFFFFFFFF`` marks an empty pixel and is the largest key; keys order as
+depths in both encodings, so the paper's dilation of inverted depth is a minimum of keys.  In stages
+1 to 4 a tap outside the image is skipped; in stage 5 it is replaced by the clamped coordinate::
+
+    1  A = min of K over the diamond |dx| + |dy| <= k
+    2  B = min of A over the square k;  C = max of B over the square k        # the closing
+    3  D = C where C != E, else min of C over the square h (fill_hole)         # h = 0: skipped
+    4  F = D where D != E, else min of D over the square g (fill_large)        # g = 0: skipped
+    5  G = E where F == E, else med = the middle of the sorted (2m+1)^2 keys of F (fill_median), E
+       sorting last; G = med if med != E else F                                # m = 0: skipped
+
+Every stage selects a key and never computes one: the result is exact in ``16UC1`` and ``32FC1``
+alike.  Departures from the paper: no extrapolation of the top rows to the top of the image, and no
+Gaussian or bilateral blur (both would compute new depths).  A filled image is not a superset of the
+unfilled one: stage 1 lets a measured pixel take a nearer neighbour's depth, as in the paper.
 """
 from __future__ import annotations
 
@@ -48,6 +68,7 @@ from .range2d import INT31, U, _xyz, project_uvw
 MAX_FRAMES = 64  # clouds per launch
 MAX_SIDE = 4096  # pixels per image side
 MAX_SPLAT = 4
+MAX_FILL = {"fill": 4, "fill_hole": 7, "fill_large": 15, "fill_median": 2}  # the radii of the hole filling
 MAX_PLANE = 256 << 20  # bytes of key plane per launch
 EMPTY = 0xFFFFFFFF  # the key of a pixel no point covers
 NAN_BITS = 0x7FC00000  # what such a pixel holds in 32FC1
@@ -69,6 +90,10 @@ class DepthOptions:
     scale: float = 1000.0
     min_depth: float = 0.5
     splat: int = 1
+    fill: int = 0  # k: 0 is off
+    fill_hole: int = 3
+    fill_large: int = 15
+    fill_median: int = 2
 
     def __post_init__(self):
         for name in ("width", "height"):
@@ -88,6 +113,10 @@ class DepthOptions:
         s = self.splat
         if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s <= MAX_SPLAT:
             raise ValueError(f"splat must be an integer in 0..{MAX_SPLAT}, got {s!r}")
+        for name, most in MAX_FILL.items():
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= most:
+                raise ValueError(f"{name} must be an integer in 0..{most}, got {v!r}")
 
     @property
     def dtype(self) -> np.dtype:
@@ -138,7 +167,84 @@ def depth_numpy(points, M, opts: DepthOptions) -> np.ndarray:
             xx, yy = px + dx, py + dy
             ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)  # the square is clipped to the image
             np.minimum.at(plane, (yy[ok], xx[ok]), key[ok])
-    return image_of_keys(plane, opts)
+    return image_of_keys(fill_numpy(plane, opts) if opts.fill else plane, opts)
+
+
+def _line(a: np.ndarray, r: int, axis: int, op, pad) -> np.ndarray:
+    """``op`` over the ``2r + 1`` taps along ``axis``; ``pad`` stands for a tap outside the plane."""
+    n = a.shape[axis]
+    width = [(r, r) if ax == axis else (0, 0) for ax in range(2)]
+    p = np.pad(a, width, constant_values=pad)
+    out = a
+    for d in range(2 * r + 1):
+        out = op(out, p[d:d + n] if axis == 0 else p[:, d:d + n])
+    return out
+
+
+def _square(a, r, op, pad):
+    return _line(_line(a, r, 1, op, pad), r, 0, op, pad)
+
+
+def fill_numpy(plane: np.ndarray, opts: DepthOptions) -> np.ndarray:
+    """The key plane (uint32 [H, W]) with its holes filled: the five stages of the module docstring."""
+    K = np.ascontiguousarray(plane, np.uint32)
+    H, W = K.shape
+    k, h, g, m = (int(v) for v in (opts.fill, opts.fill_hole, opts.fill_large, opts.fill_median))
+    E = np.uint32(EMPTY)
+    # the diamond: the row segment of half-width k - |dy| of the rows dy above and below
+    padded = {w: np.pad(_line(K, w, 1, np.minimum, E), ((k, k), (0, 0)), constant_values=E) for w in range(k)}
+    A = _line(K, k, 1, np.minimum, E)
+    for dy in range(1, k + 1):
+        p = padded[k - dy]
+        A = np.minimum(A, np.minimum(p[k - dy:k - dy + H], p[k + dy:k + dy + H]))
+    C = _square(_square(A, k, np.minimum, E), k, np.maximum, np.uint32(0))
+    D = np.where(C != E, C, _square(C, h, np.minimum, E)) if h else C
+    F = np.where(D != E, D, _square(D, g, np.minimum, E)) if g else D
+    if not m:
+        return F
+    p = np.pad(F, m, mode="edge")
+    win = np.stack([p[dy:dy + H, dx:dx + W] for dy in range(2 * m + 1) for dx in range(2 * m + 1)])
+    mid = (2 * m + 1) ** 2 // 2
+    med = np.partition(win, mid, axis=0)[mid]
+    return np.where(F == E, E, np.where(med != E, med, F)).astype(np.uint32)
+
+
+def fill_ref(plane: np.ndarray, opts: DepthOptions) -> np.ndarray:
+    """:func:`fill_numpy` by brute force: one Python loop per pixel and per tap."""
+    H, W = plane.shape
+    k, h, g, m = (int(v) for v in (opts.fill, opts.fill_hole, opts.fill_large, opts.fill_median))
+
+    def stage(src, offsets, pick):
+        out = [[0] * W for _ in range(H)]
+        for y in range(H):
+            for x in range(W):
+                taps = [src[y + dy][x + dx] for dx, dy in offsets if 0 <= x + dx < W and 0 <= y + dy < H]
+                out[y][x] = pick(src[y][x], taps)
+        return out
+
+    def square(r):
+        return [(dx, dy) for dy in range(-r, r + 1) for dx in range(-r, r + 1)]
+
+    def hole(own, taps):
+        return own if own != EMPTY else min(taps)
+
+    cur = [[int(v) for v in row] for row in plane]
+    cur = stage(cur, [(dx, dy) for dx, dy in square(k) if abs(dx) + abs(dy) <= k], lambda own, taps: min(taps))
+    cur = stage(cur, square(k), lambda own, taps: min(taps))
+    cur = stage(cur, square(k), lambda own, taps: max(taps))
+    if h:
+        cur = stage(cur, square(h), hole)
+    if g:
+        cur = stage(cur, square(g), hole)
+    if m:
+        out = [[0] * W for _ in range(H)]
+        for y in range(H):
+            for x in range(W):
+                win = sorted(cur[min(max(y + dy, 0), H - 1)][min(max(x + dx, 0), W - 1)] for dx, dy in square(m))
+                med = win[len(win) // 2]
+                out[y][x] = EMPTY if cur[y][x] == EMPTY else (med if med != EMPTY else cur[y][x])
+        cur = out
+    return np.array(cur, np.uint32).reshape(H, W)
 
 
 def depth_ref(points, M, opts: DepthOptions):
@@ -211,6 +317,7 @@ class DepthCall:
     frame_off: torch.Tensor
     frame_n: torch.Tensor
     plane: torch.Tensor  # uint8 view of B * H * W uint32 keys
+    scratch: Optional[torch.Tensor]  # another such plane when opts.fill, else None
     out: torch.Tensor  # uint8, the images back to back
     M: np.ndarray  # host float32 [12]
     layout: CloudLayout
@@ -223,15 +330,32 @@ class DepthCall:
         return self.batch * self.opts.frame_bytes
 
 
+FUSED = False  # tca_depth_fill in one launch (True) or two (profiles/depth_fill/README.md)
+
+
+def fill(c: DepthCall, stream=None, fused: Optional[bool] = None, skip_empty: bool = True) -> None:
+    """``tca_depth_fill`` alone on the keys ``tca_depth_image`` left in ``c.plane``: the filled
+    images replace ``c.out``.  ``fused`` and ``skip_empty`` are for measurements: the same bytes."""
+    p = _native.ptr
+    r = c.opts
+    n_px = c.batch * r.width * r.height
+    _native.call("tca_depth_fill", p(c.plane), 4 * n_px, c.batch, int(r.width), int(r.height), ENCODINGS[r.encoding],
+                 int(r.fill), int(r.fill_hole), int(r.fill_large), int(r.fill_median),
+                 int(FUSED if fused is None else fused), int(skip_empty), p(c.scratch), 4 * n_px, p(c.out), c.out_bytes,
+                 _native.stream_ptr(stream))
+
+
 def launch(c: DepthCall, stream=None) -> None:
-    """The launch alone (the plane's reset and the two kernels on ``stream``): no allocation,
-    no copy, no sync."""
+    """The launch alone (the plane's reset and the two kernels on ``stream``, and with
+    ``opts.fill`` K38 behind them): no allocation, no copy, no sync."""
     p = _native.ptr
     o, r = c.layout.offsets, c.opts
     _native.call("tca_depth_image", p(c.data), c.data_bytes, p(c.frame_off), p(c.frame_n), c.batch, c.max_n,
                  c.layout.point_step, o[0], o[1], o[2], c.M.ctypes.data, int(r.width), int(r.height),
                  ENCODINGS[r.encoding], float(r.scale), float(r.min_depth), int(r.splat), p(c.plane), p(c.out),
                  _native.stream_ptr(stream))
+    if r.fill:
+        fill(c, stream)
 
 
 def layout_device_ok(lay: CloudLayout) -> bool:
@@ -268,13 +392,15 @@ class DepthImager(CloudStager):
         if data_bytes >= INT31:
             raise ValueError(f"{data_bytes} payload bytes do not fit one call: split the batch")
         n_px = B * opts.width * opts.height
-        if 4 * n_px > MAX_PLANE:
-            raise ValueError(f"a key plane of {4 * n_px} bytes does not fit one call: split the batch")
+        planes = 2 if opts.fill else 1  # the keys, and K38's scratch plane
+        if 4 * planes * n_px > MAX_PLANE:
+            raise ValueError(f"a key plane of {4 * planes * n_px} bytes does not fit one call: split the batch")
         dev, _, view = self._stage("dep_in", payloads, ns, layout.point_step, misalign, (), stream)
         plane = self._device_buf("dep_plane", 4 * n_px)
+        scratch = self._device_buf("dep_scratch", 4 * n_px) if opts.fill else None
         out = self._device_buf("dep_out", B * opts.frame_bytes)
         return DepthCall(data=dev, data_bytes=data_bytes, frame_off=view("frame_off", B, torch.int64),
-                         frame_n=view("frame_n", B, torch.int32), plane=plane, out=out,
+                         frame_n=view("frame_n", B, torch.int32), plane=plane, scratch=scratch, out=out,
                          M=np.ascontiguousarray(M, np.float32).reshape(12), layout=layout, batch=B,
                          max_n=max(ns, default=0), opts=opts)
 
@@ -291,8 +417,9 @@ class DepthImager(CloudStager):
 
     def _parts(self, idx, clouds, opts: Optional[DepthOptions] = None):
         """``idx`` cut into launches of at most 64 clouds, less than 2^31 staged bytes and, with
-        ``opts``, a key plane of at most 256 MiB."""
-        most = MAX_FRAMES if opts is None else max(1, min(MAX_FRAMES, MAX_PLANE // (4 * opts.width * opts.height)))
+        ``opts``, key planes (two with ``opts.fill``) of at most 256 MiB."""
+        px = 0 if opts is None else (8 if opts.fill else 4) * opts.width * opts.height
+        most = MAX_FRAMES if opts is None else max(1, min(MAX_FRAMES, MAX_PLANE // px))
         part, size = [], 0
         for i in idx:
             nb = _align(len(clouds[i].data)) + 16
